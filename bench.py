@@ -6,7 +6,12 @@ walk fused with the fixed-vocab ZINC remap (trainer/train_agtt.py:246-254), CSR 
 One process per GPU; ranks hold their own 249,456-graph shard (weak scaling, no data-path
 collective; the optional all-gather of the padded slab is timed separately and reported beside it).
 
-    python bench.py --gpus 1 --steps 50 --warmup 5
+A plain run does only what the headline needs: corpus, warm-up (the >= 1 s sustained leg, then W steps), the K timed
+steps, the outputs of the last one (--dump-outputs), the JSON line.  --full adds every other leg: the cold start, the
+row flavours, the epoch loop, layout steps, the custom op, IBTT, the exchange legs, the boundary section, the CPU baseline.
+
+    python bench.py --gpus 1 --steps 50 --warmup 5 [--dump-outputs DIR]
+    python bench.py --gpus 1 --steps 50 --warmup 5 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -97,6 +102,29 @@ def timed_loop(fn, steps, multi, per_launch_events=True):
     wall = time.perf_counter() - t0
     ms = event_ms(pairs)
     return wall, (ms if per_launch_events else [ms[0] / steps] * steps)
+
+
+DUMP_BYTES = 56 << 20          # --dump-outputs budget: the three files stay under 64 MB
+
+
+def dump_outputs(path, ids, lens, u16, padded):
+    """What a caller of the timed step receives - the [G, ld] slab of token ids and the [G] row lengths - as float32 .npy files
+    (ids and lengths are exact in float32), with the row indices (float64) they belong to.  A slab larger than the budget is
+    sampled: the first S rows of a permutation seeded with 0, sorted, so the same arguments give the same rows.  16-bit rows are
+    read as unsigned; in the unpadded flavours the ids past a row's length are not written by the kernel and are dumped as -1."""
+    G, ld = ids.shape
+    S = min(G, DUMP_BYTES // (4 * ld + 4 + 8))
+    rows = np.arange(G) if S == G else np.sort(np.random.default_rng(0).permutation(G)[:S])
+    pick = torch.from_numpy(rows).to(ids.device)
+    sel, ln = ids.index_select(0, pick).to(torch.int32), lens.index_select(0, pick)
+    if u16:
+        sel &= 0xFFFF
+    if not padded:
+        sel = torch.where(torch.arange(ld, device=ids.device)[None, :] < ln[:, None], sel, -1)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "sent_ids.npy"), sel.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, "sent_lengths.npy"), ln.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, "sent_rows.npy"), rows.astype(np.float64))
 
 
 def boundary_section(d, G, dev, max_nodes, max_len):
@@ -321,7 +349,7 @@ def main():
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: every rank tokenizes its own ZINC-full-sized corpus (headline; no data-path collective). "
                          "strong: one corpus block-sharded over the ranks + all-gather (BASELINE config 4) becomes the headline; "
-                         "multi-rank runs report it beside the weak line either way")
+                         "multi-rank runs with --full report it beside the weak line either way")
     ap.add_argument("--cpu-sample", type=int, default=None, help="graphs in the cpu_baseline sample")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ibtt", action="store_true")
@@ -335,7 +363,14 @@ def main():
                     help="epochs (steps) one gtok_sent launch carries (gtok_sent_params.epoch_count). Default: 1 for corpora that fill "
                          "the chip on their own (zinc_full, synth_*), 24 for zinc_subset - the trainer re-tokenizes its split "
                          "every epoch and trails depend on (seed, epoch, graph) only")
+    ap.add_argument("--full", action="store_true",
+                    help="run every secondary leg beside the headline (cold start, row flavours, epoch loop, layout steps, custom op, IBTT, "
+                         "exchange legs, boundary section, CPU baseline); the --no-* options above select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0: its ids and row lengths, a seeded sample of rows when the slab "
+                         "exceeds the budget) as DIR/<name>.npy in float32 / float64")
     args = ap.parse_args()
+    full = args.full
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         os.dup2(real_stdout, 1)
         return spawn_ranks(args.gpus)
@@ -414,18 +449,20 @@ def main():
             launch(j, lens_all[j * E:j * E + cnt], count=cnt, first=first_epoch + j * E)
         return f
 
-    # the requested protocol first, from a cold start (the device idled through the CSR build): W warm-up steps, then the K
+    # --full: the requested protocol first, from a cold start (the device idled through the CSR build): W warm-up steps, then the K
     # steps - reported as `cold_start`; the headline below is measured the same way AFTER the >= 1 s leg (working clocks)
-    for w in range(-(-args.warmup // E)):
-        launch(w, scratch_len)
-    cold_wall, cold_ms = timed_loop(timed_launches(args.warmup), n_launch, multi, per_launch_events=False)
-    cold = dict(ms_per_step=round(cold_wall / args.steps * 1e3, 4), kernel_ms_per_step=round(float(np.sum(cold_ms)) / args.steps, 4),
-                graphs_per_sec=round(world * G * args.steps / cold_wall, 1),
-                note="the same W warm-up + K timed steps right after the CSR build, before the sustained leg (the r01 / r02 protocol)")
+    cold = None
+    if full:
+        for w in range(-(-args.warmup // E)):
+            launch(w, scratch_len)
+        cold_wall, cold_ms = timed_loop(timed_launches(args.warmup), n_launch, multi, per_launch_events=False)
+        cold = dict(ms_per_step=round(cold_wall / args.steps * 1e3, 4), kernel_ms_per_step=round(float(np.sum(cold_ms)) / args.steps, 4),
+                    graphs_per_sec=round(world * G * args.steps / cold_wall, 1),
+                    note="the same W warm-up + K timed steps right after the CSR build, before the sustained leg (the r01 / r02 protocol)")
     # steady state: >= 1 s of back-to-back launches (clocks, L2 / MALL state of a slab rewritten in place), one event pair
     # around all of them - reported as `sustained`.  It runs BEFORE the K timed steps of the headline, not after them: a device
     # that has been idle through the CSR build takes longer than W + K launches (~2 ms) to reach its working clocks, and the
-    # K-step figure is meant to be the rate an epoch loop sees
+    # K-step figure is meant to be the rate an epoch loop sees - so a plain run keeps it as the headline's warm-up
     sustained = None
     if not args.no_sustained:
         for w in range(3):
@@ -442,9 +479,12 @@ def main():
     # the timed region: exactly K steps (ceil(K / E) launches), barrier + synchronize on both sides, one HIP event pair around
     # the launches (roofline.kernel_ms = elapsed / launches: launch-to-launch, the ~1.5 us kernel boundary included)
     wall, kern_ms = timed_loop(timed_launches(args.warmup), n_launch, multi, per_launch_events=False)
-    # cross-check outside the timed region: the same launches with an event pair around every one (the kernel alone;
+    if args.dump_outputs and rank == 0:   # step K - 1 is epoch slice (K - 1) % E of the last launch; the legs below reuse `ids`
+        last = (args.steps - 1) % E
+        dump_outputs(args.dump_outputs, ids[last * G:(last + 1) * G], lens_all[args.steps - 1], rows_u16, rows_pad)
+    # --full, cross-check outside the timed region: the same launches with an event pair around every one (the kernel alone;
     # what rocprofv3 --kernel-trace --stats reports for it)
-    _, kern_each_ms = timed_loop(timed_launches(args.warmup), n_launch, multi)
+    kern_each_ms = timed_loop(timed_launches(args.warmup), n_launch, multi)[1] if full else None
     tmax = torch.tensor([wall], dtype=torch.float64, device=dev)
     if multi:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -452,7 +492,7 @@ def main():
     # beside the headline: the same steps with GTOK_SENT_NO_PAD (rows written up to their length only - what
     # TokenizedGraphDataset uses, its readers go through `len`); not the headline because the C ABI's documented output is the padded slab
     nopad_ms = ragged = u16_ms = u16p_ms = ragged16 = ragged16_two = ragged16_scan = ragged16_slab = epoch_loop = packed_flag = None
-    if zinc and not args.no_unpadded and not rows_u16:
+    if full and zinc and not args.no_unpadded and not rows_u16:
         per_step = lambda ms: float(np.sum(ms)) / (n_launch * E)
         _, npm = timed_loop(lambda j: launch(j, scratch_len, pad=False), n_launch, multi, per_launch_events=False)
         nopad_ms = per_step(npm)
@@ -512,7 +552,7 @@ def main():
         del ids16
     # what an epoch of the dataset classes costs on the device: Graph2TrailTokenizer.epochs_for(G) epochs per launch as 16-bit
     # rows without padding (agtt.TokenizedGraphDataset.tokenize_epoch_u16 / the tokenizer's _serve) - every workload
-    if not args.no_unpadded and not rows_u16:
+    if full and not args.no_unpadded and not rows_u16:
         Kd = gtok.Graph2TrailTokenizer.epochs_for_shape(G, ld)
         idsk = torch.empty((Kd * G, ld), dtype=torch.int16, device=dev)
         lnk = torch.empty((Kd * G,), dtype=torch.int32, device=dev)
@@ -547,16 +587,16 @@ def main():
         torch.cuda.synchronize(); t0 = time.perf_counter(); r = f(); torch.cuda.synchronize()
         return (time.perf_counter() - t0) * 1e3, r
     nbytes = lambda *ts: int(sum(t.numel() * t.element_size() for t in ts if t is not None))
-    if batch.rowptr8 is not None or (batch.lane_sorted is not None and batch.lane_sorted.rowptr8 is not None):
+    if full and (batch.rowptr8 is not None or (batch.lane_sorted is not None and batch.lane_sorted.rowptr8 is not None)):
         fb = fresh(); once(lambda: gtok.ops.pack8(fresh()))
         ms, _ = once(lambda: gtok.ops.pack8(fb))
         layout["pack8"] = dict(ms=round(ms, 3), bytes=nbytes(fb.rowptr8, fb.col8))
-    if batch.lane_sorted is not None:
+    if full and batch.lane_sorted is not None:
         fb = fresh()
         ms, sb = once(lambda: gtok.ops.lane_sorted(fb))
         layout["lane_sorted"] = dict(ms=round(ms, 3), units=sb.num_units,
                                      bytes=nbytes(sb.node_ptr, sb.edge_ptr, sb.rowptr, sb.col, sb.nattr, sb.eattr, sb.rowptr8, sb.col8, sb.graph_ids, sb.unit_ptr))
-    if batch.adj_rows is not None:
+    if full and batch.adj_rows is not None:
         fb = fresh()
         ms, _ = once(lambda: gtok.ops.adjbits(fb))
         layout["adjbits"] = dict(ms=round(ms, 3), bytes=nbytes(fb.adj_rows, fb.adj_planes))
@@ -588,7 +628,7 @@ def main():
     # the arrays torch.ops.gtok.csr_prepare hands back (prepared once, like the CSR build), and on the raw tensors alone (the op
     # prepares behind the call on first use and finds the batch again by tensor identity) - same launches, same output buffers
     torch_op = None
-    if zinc and E == 1 and not rows_u16 and rows_pad:
+    if full and zinc and E == 1 and not rows_u16 and rows_pad:
         try:
             raw = dict(node_ptr=batch.node_ptr, edge_ptr=batch.edge_ptr, rowptr=batch.rowptr, col=batch.col, nattr=batch.nattr, eattr=batch.eattr)
             t0p = time.perf_counter()
@@ -664,7 +704,7 @@ def main():
     # row come from the tokens (sent_decode); the entries behind them are taken in proportion (E_g * visited / N_g), so this
     # second yardstick is an estimate, reported beside the fixed one of SURVEY section 8d
     trunc = None
-    if not zinc and not rows_u16:
+    if full and not zinc and not rows_u16:
         step(args.warmup, scratch_len)
         # (count-only decode: capacities of 0 - the row is read to its end; round 3 passed capacities of 4 to a decoder that
         # stopped at the first entry that did not fit and reported ~5 nodes per walk where the walks reach ~68)
@@ -684,9 +724,10 @@ def main():
     roofline = dict(bound="hbm", limiter="valu_issue", kernel=kname, achieved=round(achieved, 2), peak=HBM_PEAK_GBS,
                     unit="GB/s", frac=round(achieved / HBM_PEAK_GBS, 5), traffic=traffic, traffic_source=traffic_source,
                     algorithmic_bytes_per_launch=int(read_b + write_b), kernel_ms=round(kern_s * 1e3, 4),
-                    kernel_ms_event_pair_per_launch=round(float(np.mean(kern_each_ms)), 4),
                     epochs_per_launch=E, launches=n_launch, kernel_ms_per_epoch=round(kern_s * 1e3 / epl, 5),
                     padded_slab_bytes_per_launch=int(id_bytes * G * ld * epl))
+    if kern_each_ms is not None:
+        roofline["kernel_ms_event_pair_per_launch"] = round(float(np.mean(kern_each_ms)), 4)
     if trunc is not None:
         roofline["truncation_aware"] = trunc
         if epoch_loop is not None:       # the same yardstick for the dataset classes' K-epoch launches (16-bit rows: 2 bytes per token)
@@ -708,7 +749,9 @@ def main():
                            methodology="a step = one epoch pass; K steps = ceil(K / E) gtok_sent launches of E epochs; since round 3 the >= 1 s "
                                        "sustained leg runs BEFORE the K timed steps (working clocks) - `cold_start` is the same W + K protocol "
                                        "right after the CSR build, comparable with the r01 / r02 records"),
-               roofline=roofline, cold_start=cold)
+               roofline=roofline)
+    if cold is not None:
+        out["cold_start"] = cold
     # layout steps done once per resident batch by ops.sent (outside the timed region, like the CSR build): say which were used
     layouts = [n for n, on in (("byte mirror of rowptr/col", batch.rowptr8 is not None or (batch.lane_sorted is not None and batch.lane_sorted.rowptr8 is not None)),
                                ("copy reordered by expected walk length (graph_ids + unit table)", batch.lane_sorted is not None),
@@ -742,7 +785,7 @@ def main():
 
     log("[bench] headline assembled; secondary legs follow")
     # IBTT serialiser on the same corpus (second half of the metric; outside the timed region)
-    if not args.no_ibtt:
+    if full and not args.no_ibtt:
         if zinc:
             vocab = {t: i for i, t in enumerate(
                 ["<bos>", "<eos>", "<pad>", "<unk>", "<q>", "<p>", "<atom>", "<bond>", "C", "N", "O", "F", "P", "S", "Cl",
@@ -795,7 +838,7 @@ def main():
                                          padded_slab_bytes_per_launch=int(4 * G * ild)))
 
     # the corpus pass of build_vocab_from_texts, from the CSR (graph-token corpora; outside the timed region)
-    if not zinc and not args.no_ibtt:
+    if full and not zinc and not args.no_ibtt:
         nid = max_nodes
         if nid <= 1024:
             vc = torch.zeros(nid, dtype=torch.int64, device=dev)
@@ -814,7 +857,7 @@ def main():
 
     # TokenDataset's text -> ids on the graph-token TEXT of a bounded slice of the same corpus (the
     # texts are rendered on the host, which is the slow part; outside the timed region)
-    if not zinc and not args.no_ibtt:
+    if full and not zinc and not args.no_ibtt:
         S = min(G, 4096)
         nc, ec = d["node_counts"][:S], d["edge_counts"][:S]
         eptr = np.concatenate([[0], np.cumsum(ec)])
@@ -849,7 +892,7 @@ def main():
     # collective still ends the run - the others wait until the process group's timeout.)
     def exchange_legs():
         # reassembling the padded slab on every rank: one RCCL all-gather over xGMI, timed on its own
-        if multi:
+        if full and multi:
             log("[bench] all-gather legs")
             gtok.dist.gather_tokens(ids[:G], lens[-1], world * G, 5, force=True)
             torch.cuda.synchronize(); dist.barrier()
@@ -869,7 +912,7 @@ def main():
         # BASELINE config 4 as configured: ONE ZINC-full corpus block-sharded over the ranks (strong scaling), each rank
         # tokenizes its block with graph_base = the block's first global index, one all-gather reassembles the padded slab
         # on every rank.  Reported beside the weak-scaling line above (the driver computes efficiency from `value`).
-        if multi and zinc and (args.scaling == "strong" or os.environ.get("GTOK_BENCH_STRONG", "1") == "1"):
+        if multi and zinc and (args.scaling == "strong" or (full and os.environ.get("GTOK_BENCH_STRONG", "1") == "1")):
             Gt = args.graphs or wl["graphs"]
             dc = gtok.synth.zinc_like(Gt, seed=1000)                      # the same corpus on every rank
             whole = gtok.GraphBatch.from_coo_device(dc["node_counts"], dc["edge_counts"], dc["src"], dc["dst"], dc["x"], dc["edge_attr"], device=dev)
@@ -976,7 +1019,7 @@ def main():
         out["exchange_legs_error"] = f"{type(ex).__name__}: {ex}"
 
     # throughput through the Dataset classes the trainers call (not the kernels): rank 0, N=1, ZINC-shaped workloads
-    if rank == 0 and world == 1 and zinc and not args.no_boundary:
+    if full and rank == 0 and world == 1 and zinc and not args.no_boundary:
         try:                   # a secondary section must never cost the run its headline line
             out["boundary"] = boundary_section(d, G, dev, max_nodes, max_len)
         except Exception as ex:
@@ -987,7 +1030,7 @@ def main():
         out.setdefault("boundary", {})["torch_op_sent"] = torch_op
 
     # CPU baseline: the oracle (a port, not the reference's Python) on a bounded sample, rank 0, N=1 only
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not rows_u16:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline and not rows_u16:
         try:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import oracle as orc

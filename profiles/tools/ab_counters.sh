@@ -5,7 +5,7 @@
 export TMPDIR=/tmp
 base=$1
 out=gpurun_out/ab_counters; rm -rf $out; mkdir -p $out
-B="python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-ibtt --no-unpadded --no-boundary --no-sustained"
+B="python3 bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-ibtt --no-unpadded --no-boundary --no-sustained"
 for tag in ${TAGS:-base new}; do
   lib=$PWD/glearning-benchmark_amd/csrc/libgtok.so; [ $tag = base ] && lib=$PWD/$base
   for grp in "GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAVES" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD" "SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_INST_CYCLES_SALU"; do

@@ -29,7 +29,7 @@ for wl in ("zinc_full", "synth_er", "synth_mix", "zinc_subset"):
     if not kern:
         continue
     json.dump({"command": "profiles/tools/collect.sh: rocprofv3 --kernel-trace --pmc <group> --output-format csv -- python3 bench.py "
-                          f"--steps 5 --warmup 1 --workload {wl} --no-cpu-baseline, one pass per counter group",
+                          f"--steps 5 --warmup 1 --workload {wl} --full --no-cpu-baseline, one pass per counter group",
                "note": "FETCH_SIZE / WRITE_SIZE in KiB per dispatch; hbm_bytes_per_launch = (2*FETCH + WRITE) * 1024",
                "kernels": kern}, open(f"{dst}/pmc_summary_{wl}_final.json", "w"), indent=1)
     bench = json.loads(open(f"{src}/bench_{wl}.json").read().strip().splitlines()[-1])
@@ -65,7 +65,7 @@ for rows, fname in (("unpadded", "nopad"), ("u16", "u16"), ("u16padded", "u16pad
             c["hbm_bytes_per_launch"] = int((2 * c["FETCH_SIZE"]["mean_of_last_5"] + c["WRITE_SIZE"]["mean_of_last_5"]) * 1024)
             c["write_bytes_per_launch"] = int(c["WRITE_SIZE"]["mean_of_last_5"] * 1024)
     json.dump({"command": "rocprofv3 --kernel-trace --pmc <FETCH_SIZE|WRITE_SIZE> --kernel-include-regex sent_lane -- python3 bench.py --steps 5 --warmup 1 "
-                          f"--rows {rows} ... (the timed launches run in that flavour; the <.., false> / <.., true> instantiations are the int32 / 16-bit rows)",
+                          f"--rows {rows} --full ... (the timed launches run in that flavour; the <.., false> / <.., true> instantiations are the int32 / 16-bit rows)",
                "kernels": kern}, open(f"{dst}/pmc_summary_zinc_full_{fname}.json", "w"), indent=1)
 for extra in ("check_1m.txt", "time_r04.txt"):
     if os.path.exists(f"{src}/{extra}"):

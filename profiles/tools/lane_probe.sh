@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 timeout -k 10 200 python3 profiles/tools/time_sent_zinc.py > $out/time.txt 2>&1
 cat $out/time.txt
 if [ "$2" = "pmc" ]; then
-  B="python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-ibtt"
+  B="python3 bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --no-ibtt"
   for grp in "FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_SALU SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_LDS_BANK_CONFLICT SQ_WAVES" "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INST_CYCLES_SALU SQ_ACTIVE_INST_LDS SQ_LDS_IDX_ACTIVE"; do
     name=$(echo $grp | cut -d' ' -f1)
     timeout -k 10 200 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $out/pmc_$name -o p -- $B > $out/pmc_$name.log 2>&1

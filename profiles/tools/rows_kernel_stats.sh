@@ -6,14 +6,14 @@
 export TMPDIR=/tmp
 out=gpurun_out/rows_kernel_stats; rm -rf $out; mkdir -p $out
 export GTOK_BENCH_FORCE_DIST=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29517 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench -o s -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline > $out/bench.log 2>&1 || { tail -5 $out/bench.log; exit 1; }
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench -o s -- python3 bench.py --steps 20 --warmup 3 --full --no-cpu-baseline > $out/bench.log 2>&1 || { tail -5 $out/bench.log; exit 1; }
 unset GTOK_BENCH_FORCE_DIST RANK WORLD_SIZE LOCAL_RANK
 timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $out/tests -o s -- python3 -m pytest tests/test_gpu_rows.py tests/test_gpu_boundary.py -q -x > $out/tests.log 2>&1 || { tail -5 $out/tests.log; exit 1; }
 python3 - $out <<'PY'
 import csv, glob, sys
 out = sys.argv[1]
 w = csv.writer(sys.stdout)
-for part, what in (("bench", "GTOK_BENCH_FORCE_DIST=1 ... rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline (ZINC-full: headline, row flavours, epoch loop, exchange legs, boundary section)"),
+for part, what in (("bench", "GTOK_BENCH_FORCE_DIST=1 ... rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 --warmup 3 --full --no-cpu-baseline (ZINC-full: headline, row flavours, epoch loop, exchange legs, boundary section)"),
                    ("tests", "rocprofv3 --kernel-trace --stats -- python3 -m pytest tests/test_gpu_rows.py tests/test_gpu_boundary.py (test sizes: the entry points no bench leg calls)")):
     for f in glob.glob(f"{out}/{part}/**/*kernel_stats.csv", recursive=True):
         rows = list(csv.reader(open(f)))

@@ -10,7 +10,7 @@ for sg in 2 1 4; do
   lib=$ab/libgtok_sg$sg.so; [ $sg = 2 ] && lib=$PWD/glearning-benchmark_amd/csrc/libgtok.so
   echo "== sector groups $sg"
   GTOK_LIB=$lib timeout -k 10 200 python3 profiles/tools/time_lane_ab.py 2>&1 | grep -v amdgpu.ids || exit 1
-  GTOK_LIB=$lib timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --kernel-include-regex sent_lane --output-format csv -d $out/w$sg -o p -- python3 bench.py --steps 5 --warmup 1 --rows unpadded --no-cpu-baseline --no-unpadded --no-boundary --no-sustained --no-ibtt > $out/w$sg.log 2>&1 || exit 1
+  GTOK_LIB=$lib timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --kernel-include-regex sent_lane --output-format csv -d $out/w$sg -o p -- python3 bench.py --steps 5 --warmup 1 --rows unpadded --full --no-cpu-baseline --no-unpadded --no-boundary --no-sustained --no-ibtt > $out/w$sg.log 2>&1 || exit 1
   find $out -name '*_kernel_trace.csv' -delete
   python3 profiles/tools/pmc_summary.py $out/w$sg
 done

@@ -1,5 +1,6 @@
-"""GPU: `python bench.py` keeps the driver's contract - one JSON line on stdout with the agreed keys, the
-`roofline` and `cpu_baseline` objects, and a CPU sample that matched the GPU's ids."""
+"""GPU: `python bench.py` keeps the driver's contract - one JSON line on stdout with the agreed keys; with --full the
+`roofline` and `cpu_baseline` objects and a CPU sample that matched the GPU's ids; --dump-outputs writes the last timed
+step's rows."""
 import json
 import os
 import subprocess
@@ -13,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_prints_one_contract_line():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "zinc_subset", "--steps", "3",
-                        "--warmup", "1", "--cpu-sample", "2000"], cwd=ROOT, capture_output=True, text=True, timeout=600)
+                        "--warmup", "1", "--cpu-sample", "2000", "--full"], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -40,9 +41,35 @@ def test_truncation_aware_yardstick_counts_the_nodes_the_walks_reach():
     """the decode pass behind roofline.truncation_aware stopped at its capacities (~5 nodes per walk reported
     where the walks reach ~68).  The count-only decode reads every row to its end."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "synth_er", "--graphs", "24000", "--steps", "3",
-                        "--warmup", "1", "--no-cpu-baseline", "--no-ibtt", "--no-sustained"], cwd=ROOT, capture_output=True, text=True, timeout=600)
+                        "--warmup", "1", "--no-cpu-baseline", "--no-ibtt", "--no-sustained", "--full"], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     b = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][0])
     ta = b["roofline"]["truncation_aware"]
     assert ta["avg_nodes_visited"] > 30, ta
     assert 0 < ta["bytes_per_launch"] <= b["roofline"]["algorithmic_bytes_per_launch"]
+
+
+def test_plain_run_dumps_the_last_timed_step(tmp_path):
+    """A plain run (no --full) prints the headline line without the secondary legs, and --dump-outputs writes what the
+    last of the K timed steps computed: here epoch W + K - 1, slice K - 1 of one 5-epoch launch, against the CPU oracle."""
+    import numpy as np
+    from _util import gtok, orc
+    steps, warmup = 5, 2
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "zinc_subset", "--steps", str(steps),
+                        "--warmup", str(warmup), "--dump-outputs", str(tmp_path)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    b = json.loads(lines[0])
+    assert b["metric"] == "graphs_tokenized_per_sec" and b["unit"] == "graphs/s" and b["dtype"] == "int32" and b["higher_is_better"] is True
+    assert b["steps"] == steps and b["value"] > 0 and b["ms_per_step"] > 0 and b["config"]["epochs_per_launch"] == steps
+    assert not {"cpu_baseline", "cold_start", "u16_rows", "epoch_loop", "ibtt", "boundary"} & set(b)
+    ids, ln, rows = (np.load(tmp_path / f"{n}.npy") for n in ("sent_ids", "sent_lengths", "sent_rows"))
+    assert ids.dtype == ln.dtype == np.float32 and rows.dtype == np.float64
+    assert sum(f.stat().st_size for f in tmp_path.iterdir()) <= 64 << 20
+    d = gtok.synth.zinc_like(12000, seed=1000)
+    coo = orc.Coo(d["node_counts"], d["edge_counts"], d["src"], d["dst"], d["x"], d["edge_attr"])
+    assert ids.shape == (12000, b["config"]["slab_width"]) and np.array_equal(rows, np.arange(12000))
+    ref, rln = orc.sent(coo, int(d["node_counts"].max()), 1024, 0, warmup + steps - 1, labeled=True, num_node_types=9,
+                        num_edge_types=4, remap_zinc=True, ld=ids.shape[1], nthreads=8)
+    assert np.array_equal(ln, rln) and np.array_equal(ids, ref)
