@@ -675,7 +675,18 @@ __global__ void __launch_bounds__(1024) sent_lane_kernel(const SentLaneArgs a) {
           if (kind == 2 && nvis >= n) break;
           const set_t set = kind == 0 ? row : (kind == 1 ? live : (set_t)(~vis & nodes));
 #ifndef GTOK_ABLATE_PICK
-          const int pick = kth_bit_of(set, (int)below((uint32_t)popc_of(set)));
+          // A molecule walk's choice sets mostly have <= 4 bits.  When every active lane's does, the k-th bit (k <= 3) is the
+          // lowest bit of the set with its k lowest bits cleared: three clear-lowest steps, a select and a ctz instead of the
+          // five-level search (profiles/r06/ablation.txt: 37.3 -> 36.2 M vector instructions per ZINC-full launch)
+          const int nset = popc_of(set);
+          const int kp = (int)below((uint32_t)nset);
+          int pick;
+          if (__ballot(nset > 4) == 0) {
+            const set_t x1 = set & (set - 1), x2 = x1 & (x1 - 1), x3 = x2 & (x2 - 1);
+            pick = ctz_of(kp == 0 ? set : (kp == 1 ? x1 : (kp == 2 ? x2 : x3)));
+          } else {
+            pick = kth_bit_of(set, kp);
+          }
 #else
           const int pick = ctz_of(set) + (int)(below((uint32_t)popc_of(set)) >> 31);
 #endif
@@ -719,29 +730,45 @@ __global__ void __launch_bounds__(1024) sent_lane_kernel(const SentLaneArgs a) {
           M = 0;
 #endif
           if (M) {   // LADJ, members by ascending visit index ([edge type] position), RADJ
-            bool head = true;
-            do {
-              set_t t = M;
-              int bu = 0, bv = 256;
-              do {
-                const int u = ctz_of(t);
-                t &= t - 1;
-                const int vx = snat[nbase + u];
-                if (vx < bv) { bv = vx; bu = u; }
-              } while (t);
-              M &= ~bit_of((uint32_t)bu);
-              uint32_t lo = (uint32_t)(pos_base + bv), hi = 0;
-              int cnt = 1;
+            // In 85 % of the ZINC steps that list a bracket, every lane's bracket is ONE member (profiles/r06/lockstep_stats.txt):
+            // no min-search, no loop, the four tokens in one append.  (A sorting network for up to three members - three reads
+            // at once, two appends - was measured slower than the loop: more code on the path of every bracket step for the
+            // 15 % of them with a second member; profiles/r06/README.md.)
+            if (__ballot((M & (M - 1)) != 0) == 0) {
+              const int u = ctz_of(M);
+              const uint64_t tp = (uint64_t)(pos_base + (int)snat[nbase + u]);
               if (LAB) {
-                const uint32_t at = find_et(rc, (uint32_t)bu);
-                lo = (remap ? remap_edge_type_u(at, (uint32_t)edge_off) : (uint32_t)edge_off + at) | (lo << 16);
-                cnt = 2;
+                const uint32_t at = find_et(rc, (uint32_t)u);
+                const uint64_t te = remap ? remap_edge_type_u(at, (uint32_t)edge_off) : (uint32_t)edge_off + at;
+                append((uint64_t)T_LADJ | (te << 16) | (tp << 32) | (T_RADJ << 48), 4);
+              } else {
+                append((uint64_t)T_LADJ | (tp << 16) | (T_RADJ << 32), 3);
               }
-              if (head) { hi = lo >> 16; lo = (uint32_t)T_LADJ | (lo << 16); ++cnt; head = false; }
-              uint64_t val = ((uint64_t)hi << 32) | lo;
-              if (!M) { val |= T_RADJ << (cnt << 4); ++cnt; }
-              append(val, cnt);
-            } while (M);
+            } else {
+              bool head = true;
+              do {
+                set_t t = M;
+                int bu = 0, bv = 256;
+                do {
+                  const int u = ctz_of(t);
+                  t &= t - 1;
+                  const int vx = snat[nbase + u];
+                  if (vx < bv) { bv = vx; bu = u; }
+                } while (t);
+                M &= ~bit_of((uint32_t)bu);
+                uint32_t lo = (uint32_t)(pos_base + bv), hi = 0;
+                int cnt = 1;
+                if (LAB) {
+                  const uint32_t at = find_et(rc, (uint32_t)bu);
+                  lo = (remap ? remap_edge_type_u(at, (uint32_t)edge_off) : (uint32_t)edge_off + at) | (lo << 16);
+                  cnt = 2;
+                }
+                if (head) { hi = lo >> 16; lo = (uint32_t)T_LADJ | (lo << 16); ++cnt; head = false; }
+                uint64_t val = ((uint64_t)hi << 32) | lo;
+                if (!M) { val |= T_RADJ << (cnt << 4); ++cnt; }
+                append(val, cnt);
+              } while (M);
+            }
           }
           cur = pick;
         }
