@@ -51,6 +51,26 @@ class GtokCsrSorted(ctypes.Structure):
                                                "unit_ptr", "unit_info", "info")]
 
 
+class GtokCoo(ctypes.Structure):
+    """include/gtok.h: gtok_coo - PyG collated storage, the input of gtok_csr_from_coo."""
+    _fields_ = [("num_graphs", ctypes.c_int32), ("num_source_graphs", ctypes.c_int32),
+                ("num_nodes", ctypes.c_int64), ("num_entries", ctypes.c_int64),
+                ("node_slices", ctypes.c_void_p), ("edge_slices", ctypes.c_void_p), ("indices", ctypes.c_void_p),
+                ("src", ctypes.c_void_p), ("dst", ctypes.c_void_p),
+                ("x", ctypes.c_void_p), ("x_stride", ctypes.c_int64),
+                ("edge_attr", ctypes.c_void_p), ("edge_attr_stride", ctypes.c_int64)]
+
+
+class GtokCsrBuilt(ctypes.Structure):
+    """include/gtok.h: gtok_csr_built - the output arrays of gtok_csr_from_coo."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("node_ptr", "edge_ptr", "rowptr", "col", "eorder", "nattr", "eattr", "info")]
+
+
+# gtok_csr_from_coo's input status bits (info[6])
+COO_BAD_ENDPOINT, COO_BAD_SLICES, COO_BAD_TOTALS, COO_BAD_INDEX, COO_SORT_TOO_LARGE = 1, 2, 4, 8, 16
+COO_SORT_NODES = 4096
+
+
 class GtokVocabTable(ctypes.Structure):
     _fields_ = [
         ("capacity", ctypes.c_int32), ("pad_id", ctypes.c_int32),
@@ -92,6 +112,8 @@ SYMBOLS = {
     "gtok_csr_check": (_I, [ctypes.POINTER(GtokCsr), _P, _P]),
     "gtok_csr_lane_sort_workspace": (ctypes.c_int64, [_I]),
     "gtok_csr_lane_sort": (_I, [ctypes.POINTER(GtokCsr), _I, _I, ctypes.POINTER(GtokCsrSorted), _P, ctypes.c_int64, _P]),
+    "gtok_csr_from_coo_workspace": (ctypes.c_int64, [_I, _I]),
+    "gtok_csr_from_coo": (_I, [ctypes.POINTER(GtokCoo), _I, ctypes.POINTER(GtokCsrBuilt), _P, ctypes.c_int64, _P]),
     "gtok_csr_adjbits": (_I, [ctypes.POINTER(GtokCsr), _I, _P, _P, _P, _P]),
     "gtok_csr_pack8": (_I, [ctypes.POINTER(GtokCsr), ctypes.c_int64, ctypes.c_int64, _P, _P, _P]),
     "gtok_row_offsets": (_I, [_P, ctypes.c_int64, _I, _I, _P, _P]),
@@ -171,7 +193,7 @@ _lib = None
 _lib_version = 0
 
 
-ABI_VERSION = 6     # include/gtok.h: GTOK_ABI_VERSION
+ABI_VERSION = 7     # include/gtok.h: GTOK_ABI_VERSION
 
 
 def lib() -> ctypes.CDLL:

@@ -205,12 +205,25 @@ class GraphBatch:
 
     @staticmethod
     def from_coo_device(node_counts, edge_counts, src, dst, x=None, edge_attr=None, device="cuda",
-                        check_symmetric: bool = True) -> "GraphBatch":
-        """from_coo() with the heavy passes (row sort, row pointers, symmetry check) done by torch on the GPU:
-        the same arrays, bit for bit, built in milliseconds instead of seconds for 10^8-entry corpora, and left on
-        the device.  Inputs may be numpy arrays or tensors (host or device); src / dst are LOCAL node ids, the edges of
-        graph g contiguous and in edge_index order."""
+                        check_symmetric: bool = True, builder: str = "auto") -> "GraphBatch":
+        """from_coo() with the heavy passes (row sort, row pointers, symmetry check) done on the GPU: the same arrays,
+        bit for bit, built in milliseconds instead of seconds for 10^8-entry corpora, and left on the device.  Inputs may
+        be numpy arrays or tensors (host or device); src / dst are LOCAL node ids, the edges of graph g contiguous and in
+        edge_index order.  builder: "auto" builds with gtok_csr_from_coo (ops.csr_from_coo) on a gfx950 device, "torch"
+        with the chain of torch operations below (the A/B comparator; also what "auto" does elsewhere).  An input the HIP
+        build reports as damaged (or an unsorted graph too large for its sort) is built again by the torch chain, so the
+        results and the exceptions are the same whichever builder runs."""
+        if builder not in ("auto", "torch"):
+            raise ValueError('builder must be "auto" or "torch"')
         dev = torch.device(device)
+        if builder == "auto" and _hip_builder_ok(dev):
+            b = _from_coo_hip(node_counts, edge_counts, src, dst, x, edge_attr, dev, check_symmetric)
+            if b is not None:
+                return b
+        return GraphBatch._from_coo_torch(node_counts, edge_counts, src, dst, x, edge_attr, dev, check_symmetric)
+
+    @staticmethod
+    def _from_coo_torch(node_counts, edge_counts, src, dst, x, edge_attr, dev, check_symmetric) -> "GraphBatch":
         t64 = lambda a: torch.as_tensor(a).reshape(-1).to(dev, dtype=torch.int64)
         nc, ec, s, d = t64(node_counts), t64(edge_counts), t64(src), t64(dst)
         G = int(nc.numel())
@@ -292,6 +305,10 @@ class GraphBatch:
         xa = None if x is None else t(x).reshape(t(x).shape[0], -1)[:, 0]
         ea = None if edge_attr is None else t(edge_attr).reshape(-1)
         src, dst = ei[0], ei[1]
+        bdev = ei.device if device is None else torch.device(device)
+        if ei.device.type == "cuda" and bdev.type == "cuda" and _hip_builder_ok(bdev):
+            # storage already in HBM: built where it is (gtok_csr_from_coo, the subset through `indices`), never copied to the host
+            return _from_collated_device(nc, es, src, dst, xa, ea, indices, bdev, check_symmetric)
         if indices is not None:
             idx = torch.as_tensor(list(indices) if not torch.is_tensor(indices) else indices, dtype=torch.int64).reshape(-1)
             nptr = torch.zeros(nc.numel() + 1, dtype=torch.int64); torch.cumsum(nc, 0, out=nptr[1:])
@@ -388,6 +405,87 @@ class GraphBatch:
                     a = np.asarray(p, dtype=np.int64).reshape(-1)[:ecs[g]]
                     eas[eptr[g]:eptr[g] + a.size] = a
         return GraphBatch.from_coo(ncs, ecs, ei[0], ei[1], xs, eas)
+
+
+_HIP_BUILDER: dict = {}
+
+
+def _hip_builder_ok(dev: torch.device) -> bool:
+    """The HIP builder runs on a gfx950 device with the library loaded (answered once per device)."""
+    if dev.type != "cuda":
+        return False
+    key = dev.index if dev.index is not None else -1
+    ok = _HIP_BUILDER.get(key)
+    if ok is None:
+        try:
+            from . import _lib
+            _lib.lib()
+            d = dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+            ok = torch.cuda.is_available() and torch.cuda.get_device_properties(d).gcnArchName.split(":")[0] == "gfx950"
+        except Exception:
+            ok = False
+        _HIP_BUILDER[key] = ok
+    return ok
+
+
+def _host_sum(a) -> Optional[int]:
+    """Sum of a host-held array of counts (numpy, list, CPU tensor); None when it lives on a device."""
+    if torch.is_tensor(a):
+        return int(a.sum()) if a.device.type == "cpu" else None
+    return int(np.asarray(a, dtype=np.int64).sum())
+
+
+def _from_coo_hip(node_counts, edge_counts, src, dst, x, edge_attr, dev, check_symmetric) -> Optional[GraphBatch]:
+    """from_coo_device through gtok_csr_from_coo, or None when the torch chain has to take this input (it then raises what it
+    always raised, or builds what the kernel declined)."""
+    from . import ops
+    nc, ec = torch.as_tensor(node_counts).reshape(-1), torch.as_tensor(edge_counts).reshape(-1)
+    s, d = torch.as_tensor(src).reshape(-1), torch.as_tensor(dst).reshape(-1)
+    G = int(nc.numel())
+    if G == 0 or ec.numel() != G or s.numel() != d.numel():
+        return None
+    E = int(s.numel())
+    N = _host_sum(nc)
+    xa = None if x is None else torch.as_tensor(x).reshape(-1)
+    ea = None if edge_attr is None else torch.as_tensor(edge_attr).reshape(-1)
+    if N is None:
+        N = int(xa.numel()) if xa is not None else int(nc.to(dev).sum())    # (the torch chain reads the total back too)
+    if (xa is not None and xa.numel() != N) or (ea is not None and ea.numel() != E) or N + G >= 2 ** 31:
+        return None
+    t64 = lambda a: a.to(dev, dtype=torch.int64)
+    ns = torch.zeros(G + 1, dtype=torch.int64, device=dev); torch.cumsum(t64(nc), 0, out=ns[1:])
+    es = torch.zeros(G + 1, dtype=torch.int64, device=dev); torch.cumsum(t64(ec), 0, out=es[1:])
+    return ops._csr_from_coo(s, d, ns, es, xa, ea, None, check_symmetric, N, E, dev)[0]
+
+
+def _from_collated_device(nc, es, src, dst, xa, ea, indices, dev, check_symmetric) -> GraphBatch:
+    """from_collated of storage held on the device: gtok_csr_from_coo over the storage, the subset through `indices`."""
+    from . import ops
+    S = int(nc.numel())
+    ns = torch.zeros(S + 1, dtype=torch.int64, device=nc.device); torch.cumsum(nc, 0, out=ns[1:])
+    idx = None
+    if indices is not None:
+        idx = indices if torch.is_tensor(indices) else torch.as_tensor(list(indices), dtype=torch.int64)
+    N = E = None
+    if idx is None:
+        E = int(src.numel())
+    if ns.device.type == "cpu" and es.device.type == "cpu":
+        if idx is None:
+            N = int(ns[-1])
+        else:
+            ii = idx.reshape(-1).to(torch.int64).cpu()
+            if ii.numel() and (int(ii.min()) < 0 or int(ii.max()) >= S):
+                raise IndexError("indices outside the storage")
+            N, E = int((ns[1:] - ns[:-1])[ii].sum()), int((es[1:] - es[:-1])[ii].sum())
+    b, status = ops._csr_from_coo(src, dst, ns, es, xa, ea, idx, check_symmetric, N, E, dev)
+    if status:
+        if idx is None:                  # what the build path always did with such input: the torch chain's exception
+            if int(es[0]) != 0 or int(es[-1]) != src.numel():
+                raise ValueError("edge_slices does not cover edge_index")
+            return GraphBatch.from_coo_device(nc, es[1:] - es[:-1], src, dst, xa, ea, device=dev, check_symmetric=check_symmetric,
+                                              builder="torch")
+        raise ops.CooInputError(status)
+    return b
 
 
 def collated_storage(dataset):

@@ -9,6 +9,8 @@
 //                        units of <= 64 graphs whose staged bytes fit a wave's LDS share: graph_ids / unit_ptr / unit_info,
 //                        the permuted CSR arrays and their byte mirror) - counting sort + single-pass scans + a
 //                        block-wise pointer chase, twelve small launches, no host round trip
+//   gtok_csr_from_coo    the batched CSR itself, from PyG collated storage (edge_index with local ids + slices + optional
+//                        indices): what GraphBatch.from_coo does on the host, in four launches, no host round trip
 //
 // Everything here is integer bookkeeping over arrays of a few MB: the kernels are bound by launch gaps and by the
 // latency of dependent loads, not by HBM; their job is to cost well under one epoch of tokenization, once.
@@ -102,6 +104,43 @@ __device__ __forceinline__ void scan_group_staged(const CsrScanArgs &a, const in
   }
 }
 
+// The general path's examination of ONE row: row u of a graph of n nodes and eg entries whose n + 1 row pointers are rpg and
+// whose entries are c.  Returns the row's length (0 for a malformed row pointer, counted as a violation); CHECK adds the entry
+// checks (range, self loop, repeat, reverse entry).  Also the large-graph check of gtok_csr_from_coo.
+template <bool CHECK>
+__device__ __forceinline__ int scan_row_general(const int32_t *__restrict__ rpg, const int32_t *__restrict__ c, int u, int n, int eg, int &viol) {
+  const int rs = rpg[u], re = rpg[u + 1];
+  const bool bad = rs < 0 || re < rs || re > eg || (u == 0 && rs != 0) || (u == n - 1 && re != eg);
+  const int deg = bad ? 0 : re - rs;
+  viol += bad;
+  if (CHECK && !bad) {
+    int prev = -1;
+    bool sorted = true;
+    for (int j = rs; j < re; ++j) {
+      const int x = c[j];
+      if (x < 0 || x >= n || x == u) { ++viol; continue; }            // out of range, or a self loop
+      if (!sorted || x <= prev) {                                     // rows usually ascend (then no entry repeats); else compare
+        sorted = false;
+        for (int jj = rs; jj < j; ++jj) if (c[jj] == x) { ++viol; break; }
+      }
+      prev = x;
+      const int ws = rpg[x], we = rpg[x + 1];                         // (u, x) needs (x, u)
+      if (ws < 0 || we < ws || we > eg) { ++viol; continue; }
+      int b0 = ws, b1 = we;
+      bool found = false;
+      while (b0 < b1) {                                               // bisection is right when that row ascends ...
+        const int mid = (b0 + b1) >> 1, y = c[mid];
+        if (y == u) { found = true; break; }
+        if (y < u) b0 = mid + 1; else b1 = mid;
+      }
+      if (!found)                                                     // ... and a scan settles it when it does not
+        for (int jj = ws; jj < we; ++jj) if (c[jj] == u) { found = true; break; }
+      viol += !found;
+    }
+  }
+  return deg;
+}
+
 template <bool CHECK>
 __global__ void __launch_bounds__(256) csr_scan_kernel(const CsrScanArgs a) {
   extern __shared__ __align__(16) unsigned char scan_smem[];
@@ -138,38 +177,9 @@ __global__ void __launch_bounds__(256) csr_scan_kernel(const CsrScanArgs a) {
       while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (np[mid] <= v) lo = mid; else hi = mid - 1; }
       const int k = lo, u = v - np[k], n = np[k + 1] - np[k], eg = (int)(ep[k + 1] - ep[k]);
       const int32_t *__restrict__ rpg = a.rowptr + (int64_t)np[k] + g0 + k;     // the graph's n + 1 row pointers
-      const int rs = rpg[u], re = rpg[u + 1];
-      const bool bad = rs < 0 || re < rs || re > eg || (u == 0 && rs != 0) || (u == n - 1 && re != eg);
-      const int deg = bad ? 0 : re - rs;
-      viol += bad;
+      const int deg = scan_row_general<CHECK>(rpg, CHECK ? a.col + ep[k] : nullptr, u, n, eg, viol);
       maxdeg = max(maxdeg, deg);
       if (deg == 1) atomicAdd(&lf[k], 1);
-      if (CHECK && !bad) {
-        const int32_t *__restrict__ c = a.col + ep[k];
-        int prev = -1;
-        bool sorted = true;
-        for (int j = rs; j < re; ++j) {
-          const int x = c[j];
-          if (x < 0 || x >= n || x == u) { ++viol; continue; }            // out of range, or a self loop
-          if (!sorted || x <= prev) {                                     // rows usually ascend (then no entry repeats); else compare
-            sorted = false;
-            for (int jj = rs; jj < j; ++jj) if (c[jj] == x) { ++viol; break; }
-          }
-          prev = x;
-          const int ws = rpg[x], we = rpg[x + 1];                         // (u, x) needs (x, u)
-          if (ws < 0 || we < ws || we > eg) { ++viol; continue; }
-          int b0 = ws, b1 = we;
-          bool found = false;
-          while (b0 < b1) {                                               // bisection is right when that row ascends ...
-            const int mid = (b0 + b1) >> 1, y = c[mid];
-            if (y == u) { found = true; break; }
-            if (y < u) b0 = mid + 1; else b1 = mid;
-          }
-          if (!found)                                                     // ... and a scan settles it when it does not
-            for (int jj = ws; jj < we; ++jj) if (c[jj] == u) { found = true; break; }
-          viol += !found;
-        }
-      }
     }
   }
   wave_sync();
@@ -586,6 +596,321 @@ static LaneSortWs lane_sort_ws(int64_t G) {
   return w;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// gtok_csr_from_coo: the batched CSR from PyG collated storage (edge_index with LOCAL ids + slices), three launches after
+// the initialiser:
+//   coo_ptr_kernel     per graph: resolve `indices`, validate the slices, counts -> node_ptr / edge_ptr (decoupled look-back
+//                      over tiles of kPtrTile graphs, tiles numbered by ticket), max_nodes / max_edges / 64-graph chunk maxima,
+//                      the declared totals against the scanned ones (last tile)
+//   coo_build_kernel   one wave per graph: streams the graph's entries (coalesced int64 loads), validates the endpoints, writes
+//                      col / eattr / identity eorder and the row pointers as if the rows were sorted (a row starts where its
+//                      first entry is: rows (previous row, this row] start at this entry), notes whether they were; nattr;
+//                      the symmetry check of graphs of <= kCooBitN nodes through a bit matrix in LDS
+//   coo_fix_kernel     one wave per 64 graphs: the graphs the build found unsorted get a stable counting sort in LDS (nodes
+//                      <= kCooSortN), the graphs too large for a bit matrix get the general check of gtok_csr_check on the
+//                      finished arrays; max_degree and info[7]
+// A graph's damaged input raises a status bit in info[6]; slices, totals and indices that are damaged stop the last two
+// kernels before they read through them (nothing is read or written outside the declared ranges).
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int kInfoCooChunkN = 4, kInfoCooChunkE = 5, kInfoStatus = 6, kInfoSorted = 7;
+constexpr int kCooFatal = GTOK_COO_BAD_SLICES | GTOK_COO_BAD_TOTALS | GTOK_COO_BAD_INDEX;
+constexpr int kCooBitN = 256;                           // bit matrix of graphs up to this many nodes: 8 KB of LDS per wave
+constexpr int kCooBitWords = kCooBitN * kCooBitN / 32;
+constexpr int kCooSortN = GTOK_COO_SORT_NODES;                       // the counting sort's row cursors: 16 KB of LDS per wave
+constexpr int kCooU = 8;                                // chunks of 64 entries whose loads are in flight together
+
+struct CooArgs {
+  const int64_t *node_slices, *edge_slices, *indices, *src, *dst, *x, *ea;
+  int64_t x_stride, ea_stride, N, E;
+  int G, S, check;
+  int32_t *node_ptr; int64_t *edge_ptr; int32_t *rowptr, *col, *eorder; uint8_t *nattr, *eattr; int32_t *info;
+  int64_t *nsrc, *esrc;                                 // workspace: every graph's first node / entry in the storage
+  int32_t *gdeg; uint8_t *gneed;                        // workspace: longest sorted run, what coo_fix_kernel must do
+  int64_t *st_n, *st_e; int *ticket;
+};
+
+constexpr uint8_t kNeedSort = 1, kNeedCheck = 2;
+
+__device__ __forceinline__ uint8_t type_u8(int64_t v) { return (v >= 0 && v < 255) ? (uint8_t)v : (uint8_t)255; }
+
+__global__ void __launch_bounds__(256) coo_ptr_kernel(const CooArgs a) {
+  __shared__ int s_tile;
+  __shared__ int64_t s_wn[4], s_we[4], s_base[2];
+  const int tid = (int)threadIdx.x, lane = lane_id(), w = tid >> 6;
+  if (tid == 0) s_tile = atomicAdd(a.ticket, 1);
+  __syncthreads();
+  const int tile = s_tile;
+  const int64_t i0 = (int64_t)tile * kPtrTile + tid * 4;
+  int bad = 0;
+  int64_t nv[4], ev[4], tn = 0, te = 0, mn = 0, me = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int64_t i = i0 + k;
+    nv[k] = ev[k] = 0;
+    if (i < a.G) {
+      const int64_t s = a.indices ? a.indices[i] : i;
+      if (s < 0 || s >= a.S) {
+        bad |= GTOK_COO_BAD_INDEX;
+      } else {
+        const int64_t n0 = a.node_slices[s], n1 = a.node_slices[s + 1], e0 = a.edge_slices[s], e1 = a.edge_slices[s + 1];
+        if (n1 < n0 || e1 < e0 || n1 - n0 > 0x7FFFFFFF || e1 - e0 > 0x7FFFFFFF) bad |= GTOK_COO_BAD_SLICES;
+        else { nv[k] = n1 - n0; ev[k] = e1 - e0; }
+        a.nsrc[i] = n0; a.esrc[i] = e0;
+      }
+    }
+    tn += nv[k]; te += ev[k];
+    mn = max(mn, nv[k]); me = max(me, ev[k]);
+  }
+  if (a.indices)                                        // storage graphs nobody picked still have to be well-formed slices
+    for (int64_t s = (int64_t)blockIdx.x * 256 + tid; s < a.S; s += (int64_t)gridDim.x * 256)
+      if (a.node_slices[s + 1] < a.node_slices[s] || a.edge_slices[s + 1] < a.edge_slices[s]) bad |= GTOK_COO_BAD_SLICES;
+  if (tile == 0 && tid == 0 && (a.node_slices[0] != 0 || a.edge_slices[0] != 0)) bad |= GTOK_COO_BAD_SLICES;
+  int64_t in_n = tn, in_e = te;
+#pragma unroll
+  for (int o = 1; o < kWave; o <<= 1) {
+    const int64_t un = __shfl_up(in_n, o), ue = __shfl_up(in_e, o);
+    if (lane >= o) { in_n += un; in_e += ue; }
+  }
+  if (lane == kWave - 1) { s_wn[w] = in_n; s_we[w] = in_e; }
+  // 64-graph chunks: 16 lanes hold one (tiles start at multiples of 1024 graphs)
+  int64_t cn = tn, ce = te;
+#pragma unroll
+  for (int o = 1; o < 16; o <<= 1) { cn += __shfl_xor(cn, o); ce += __shfl_xor(ce, o); }
+  __syncthreads();
+  if (w == 0) {
+    const int64_t sn = s_wn[0] + s_wn[1] + s_wn[2] + s_wn[3], se = s_we[0] + s_we[1] + s_we[2] + s_we[3];
+    const int64_t xn = lookback_exclusive(a.st_n, tile, sn), xe = lookback_exclusive(a.st_e, tile, se);
+    if (lane == 0) {
+      s_base[0] = xn; s_base[1] = xe;
+      if (tile == (int)gridDim.x - 1 && (xn + sn != a.N || xe + se != a.E)) atomicOr(a.info + kInfoStatus, GTOK_COO_BAD_TOTALS);
+    }
+  }
+  __syncthreads();
+  int64_t rn = s_base[0] + in_n - tn, re = s_base[1] + in_e - te;
+  for (int k = 0; k < w; ++k) { rn += s_wn[k]; re += s_we[k]; }
+  if (tile == 0 && tid == 0) { a.node_ptr[0] = 0; a.edge_ptr[0] = 0; }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    rn += nv[k]; re += ev[k];
+    if (i0 + k < a.G) { a.node_ptr[i0 + k + 1] = (int32_t)rn; a.edge_ptr[i0 + k + 1] = re; }
+  }
+  // (counts are < 2^31 each; a sum that is not is a wrong total, flagged above)
+  const int wmn = wave_max((int)mn), wme = wave_max((int)me);
+  const int wcn = wave_max((int)min(cn, (int64_t)0x7FFFFFFF)), wce = wave_max((int)min(ce, (int64_t)0x7FFFFFFF));
+  const uint64_t anybad = __ballot(bad != 0);
+  int allbad = bad;
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) allbad |= __shfl_xor(allbad, o);
+  if (lane == 0) {
+    raise_max(a.info + kInfoMaxN, wmn);
+    raise_max(a.info + kInfoMaxE, wme);
+    raise_max(a.info + kInfoCooChunkN, wcn);
+    raise_max(a.info + kInfoCooChunkE, wce);
+    if (anybad) atomicOr(a.info + kInfoStatus, allbad);
+  }
+}
+
+__global__ void __launch_bounds__(256) coo_build_kernel(const CooArgs a) {
+  __shared__ uint32_t s_bits[4][kCooBitWords];
+  const int lane = lane_id(), w = wave_id();
+  const int64_t gl = (int64_t)blockIdx.x * 4 + w;
+  if (gl >= a.G) return;
+  if (a.info[kInfoStatus] & kCooFatal) return;         // (written by coo_ptr_kernel, which has finished)
+  const int g = (int)gl;
+  const int32_t nb = a.node_ptr[g];
+  const int n = a.node_ptr[g + 1] - nb;
+  const int64_t E0 = a.edge_ptr[g], es = a.esrc[g], ns = a.nsrc[g];
+  const int e = (int)(a.edge_ptr[g + 1] - E0);
+  int32_t *__restrict__ rp = a.rowptr + (int64_t)nb + g;
+  const bool bits = a.check && n <= kCooBitN;
+  uint32_t *bm = s_bits[w];
+  if (bits) {
+    const int nw = (n * n + 31) >> 5;
+    for (int i = lane; i < nw; i += kWave) bm[i] = 0;
+    wave_sync();
+  }
+  if (a.nattr)
+    for (int j = lane; j < n; j += kWave) a.nattr[(int64_t)nb + j] = type_u8(a.x[(ns + j) * a.x_stride]);
+  int viol = 0, maxdeg = 0, prev = -1, runstart = 0;
+  bool bad = false, unsorted = false;
+  int64_t sv[kCooU], dv[kCooU];
+  for (int t0 = 0; t0 < e; t0 += kCooU * kWave) {
+    int64_t av[kCooU];
+#pragma unroll
+    for (int j = 0; j < kCooU; ++j) {
+      const int t = t0 + j * kWave + lane;
+      sv[j] = dv[j] = av[j] = 0;
+      if (t < e) {
+        sv[j] = a.src[es + t]; dv[j] = a.dst[es + t];
+        if (a.eattr) av[j] = a.ea[(es + t) * a.ea_stride];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kCooU; ++j) {
+      const int tb = t0 + j * kWave;
+      if (tb >= e) break;
+      const int t = tb + lane;
+      const bool on = t < e;
+      const bool ok = on && sv[j] >= 0 && sv[j] < n && dv[j] >= 0 && dv[j] < n;
+      bad |= on && !ok;
+      const int s = ok ? (int)sv[j] : -1, d = ok ? (int)dv[j] : 0;
+      int p = __shfl_up(s, 1);
+      if (lane == 0) p = prev;
+      unsorted |= on && s < p;
+      if (on) for (int r = p + 1; r <= s; ++r) rp[r] = t;          // rows (p, s] start at this entry (when the rows ascend)
+      int rs = (on && s != p) ? t : -1;                            // the start of this entry's run of equal rows
+#pragma unroll
+      for (int o = 1; o < kWave; o <<= 1) { const int up = __shfl_up(rs, o); if (lane >= o) rs = max(rs, up); }
+      rs = max(rs, runstart);
+      if (on) {
+        maxdeg = max(maxdeg, t - rs + 1);
+        a.col[E0 + t] = d;
+        a.eorder[E0 + t] = t;
+        if (a.eattr) a.eattr[E0 + t] = type_u8(av[j]);
+      }
+      if (bits && ok) {
+        if (s == d) ++viol;                                        // a self loop
+        else {
+          const int bit = s * n + d;
+          const uint32_t m = 1u << (bit & 31);
+          viol += (atomicOr(&bm[bit >> 5], m) & m) != 0;           // listed twice
+        }
+      }
+      const int last = min(kWave - 1, e - 1 - tb);
+      prev = __shfl(s, last); runstart = __shfl(rs, last);
+    }
+  }
+  for (int r = prev + 1 + lane; r <= n; r += kWave) rp[r] = e;    // rows after the last entry's (all of them when e == 0)
+  if (bits && e > 0) {                                             // (v, u) for every (u, v)
+    wave_sync();
+    for (int t0 = 0; t0 < e; t0 += kCooU * kWave) {
+      if (e > kCooU * kWave) {
+#pragma unroll
+        for (int j = 0; j < kCooU; ++j) {
+          const int t = t0 + j * kWave + lane;
+          sv[j] = dv[j] = -1;
+          if (t < e) { sv[j] = a.src[es + t]; dv[j] = a.dst[es + t]; }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < kCooU; ++j) {
+        const int t = t0 + j * kWave + lane;
+        if (t < e && sv[j] >= 0 && sv[j] < n && dv[j] >= 0 && dv[j] < n && sv[j] != dv[j]) {
+          const int bit = (int)dv[j] * n + (int)sv[j];
+          viol += ((bm[bit >> 5] >> (bit & 31)) & 1u) == 0;
+        }
+      }
+    }
+  }
+  const int vs = (int)wave_sum64(viol), md = wave_max(maxdeg);
+  const bool any_bad = __ballot(bad) != 0, any_uns = __ballot(unsorted) != 0;
+  if (lane == 0) {
+    a.gdeg[g] = md;
+    a.gneed[g] = (any_uns ? kNeedSort : 0) | ((a.check && n > kCooBitN) ? kNeedCheck : 0);
+    if (vs) atomicAdd(a.info + kInfoViol, vs);
+    if (any_bad) atomicOr(a.info + kInfoStatus, GTOK_COO_BAD_ENDPOINT);
+  }
+}
+
+__global__ void __launch_bounds__(256) coo_fix_kernel(const CooArgs a) {
+  __shared__ int32_t s_cur[4][kCooSortN];
+  const int lane = lane_id(), w = wave_id();
+  const int64_t g0l = ((int64_t)blockIdx.x * 4 + w) * 64;
+  if (g0l >= a.G) return;
+  if (a.info[kInfoStatus] & kCooFatal) return;
+  const int g0 = (int)g0l, cnt = min(64, a.G - g0);
+  int md = 0, need = 0;
+  if (lane < cnt) { md = a.gdeg[g0 + lane]; need = a.gneed[g0 + lane]; }
+  uint64_t todo = __ballot(need != 0);
+  const bool any_sorted = __ballot(need & kNeedSort) != 0;
+  int viol = 0, status = 0;
+  int32_t *cur = s_cur[w];
+  while (todo) {
+    const int k = __builtin_ctzll(todo);
+    todo &= todo - 1;
+    const int g = g0 + k, nd = __shfl(need, k);
+    const int32_t nb = a.node_ptr[g];
+    const int n = a.node_ptr[g + 1] - nb;
+    const int64_t E0 = a.edge_ptr[g], es = a.esrc[g];
+    const int e = (int)(a.edge_ptr[g + 1] - E0);
+    int32_t *__restrict__ rp = a.rowptr + (int64_t)nb + g;
+    if (nd & kNeedSort) {
+      if (n > kCooSortN) { status |= GTOK_COO_SORT_TOO_LARGE; continue; }
+      for (int r = lane; r < n; r += kWave) cur[r] = 0;
+      wave_sync();
+      for (int t = lane; t < e; t += kWave) {
+        const int64_t s = a.src[es + t];
+        if (s >= 0 && s < n) atomicAdd(&cur[s], 1);
+      }
+      wave_sync();
+      int carry = 0;
+      for (int r0 = 0; r0 < n; r0 += kWave) {                      // row starts: exclusive scan of the degrees
+        const int r = r0 + lane;
+        const int v = r < n ? cur[r] : 0;
+        md = max(md, v);
+        int inc = v;
+#pragma unroll
+        for (int o = 1; o < kWave; o <<= 1) { const int up = __shfl_up(inc, o); if (lane >= o) inc += up; }
+        if (r < n) { cur[r] = carry + inc - v; rp[r] = carry + inc - v; }
+        carry += __shfl(inc, kWave - 1);
+      }
+      wave_sync();
+      const int nbits = n > 1 ? 32 - __builtin_clz((unsigned)(n - 1)) : 0;
+      for (int t0 = 0; t0 < e; t0 += kWave) {                      // stable: entries in list order, 64 at a time
+        const int t = t0 + lane;
+        int64_t s = -1, d = 0, av = 0;
+        if (t < e) { s = a.src[es + t]; d = a.dst[es + t]; if (a.eattr) av = a.ea[(es + t) * a.ea_stride]; }
+        const bool valid = s >= 0 && s < n;
+        const int key = valid ? (int)s : 0;
+        uint64_t m = __ballot(valid);                                // the lanes that hold this lane's row: one ballot per bit
+        for (int b = 0; b < nbits; ++b) {
+          const bool bit = (key >> b) & 1;
+          const uint64_t bal = __ballot(bit);
+          m &= bit ? bal : ~bal;
+        }
+        const int prior = valid ? cur[key] : 0;
+        wave_sync();
+        if (valid && lane == __builtin_ctzll(m)) cur[key] = prior + __popcll(m);
+        wave_sync();
+        if (valid) {
+          const int64_t at = E0 + prior + __popcll(m & lanemask_lt());
+          a.col[at] = (int32_t)d;
+          a.eorder[at] = t;
+          if (a.eattr) a.eattr[at] = type_u8(av);
+        }
+      }
+      if (nd & kNeedCheck) __threadfence();                        // the check below reads what this wave has just written
+    }
+    if (nd & kNeedCheck)
+      for (int u = lane; u < n; u += kWave) md = max(md, scan_row_general<true>(rp, a.col + E0, u, n, e, viol));
+  }
+  const int vs = (int)wave_sum64(viol), wmd = wave_max(md);
+  if (lane == 0) {
+    raise_max(a.info + kInfoMaxDeg, wmd);
+    if (any_sorted) atomicOr(a.info + kInfoSorted, 1);
+    if (vs) atomicAdd(a.info + kInfoViol, vs);
+    if (status) atomicOr(a.info + kInfoStatus, status);
+  }
+}
+
+// workspace layout of gtok_csr_from_coo (every region 16-byte aligned)
+struct CooWs { int64_t nsrc, esrc, gdeg, gneed, st_n, st_e, ticket, total; int tiles; };
+static CooWs coo_ws(int64_t G) {
+  CooWs w;
+  auto up = [](int64_t v) { return (v + 15) / 16 * 16; };
+  w.tiles = (int)((G + kPtrTile - 1) / kPtrTile);
+  int64_t off = 0;
+  w.nsrc = off; off += up(8 * G);
+  w.esrc = off; off += up(8 * G);
+  w.gdeg = off; off += up(4 * G);
+  w.gneed = off; off += up(G);
+  w.st_n = off; off += 8ll * w.tiles;
+  w.st_e = off; off += up(8ll * w.tiles);       // (st_n and st_e are one run of 2 * tiles words for the initialiser)
+  w.ticket = off; off += 16;
+  w.total = off;
+  return w;
+}
+
 }  // namespace gtok
 
 using namespace gtok;
@@ -656,5 +981,53 @@ extern "C" int gtok_csr_lane_sort(const gtok_csr *g, int32_t lds_budget, int32_t
   hipLaunchKernelGGL(unit_chase_kernel, dim3(1), dim3(256), 0, s, table, w.ublocks, G, entry, ubase, o->unit_ptr, o->info);
   hipLaunchKernelGGL(unit_write_kernel, dim3(w.ublocks), dim3(64), 0, s, hop, G, entry, ubase, o->unit_ptr);
   hipLaunchKernelGGL(unit_info_kernel, dim3(ngroups), dim3(256), 0, s, o->unit_ptr, o->node_ptr, o->edge_ptr, o->unit_info, o->info);
+  return hipGetLastError() == hipSuccess ? GTOK_OK : GTOK_E_LAUNCH;
+}
+
+extern "C" int64_t gtok_csr_from_coo_workspace(int32_t num_graphs, int32_t num_source_graphs) {
+  (void)num_source_graphs;
+  return num_graphs <= 0 ? 16 : coo_ws(num_graphs).total;
+}
+
+extern "C" int gtok_csr_from_coo(const gtok_coo *in, int32_t check, const gtok_csr_built *out, void *workspace, int64_t workspace_bytes,
+                                 void *stream) {
+  DeviceScope device_scope((hipStream_t)stream);
+  if (!device_scope.ok()) return GTOK_E_NO_DEVICE;
+  if (!in || !out || !out->info || !out->node_ptr || !out->edge_ptr) return GTOK_E_INVAL;
+  const int G = in->num_graphs, S = in->num_source_graphs;
+  if (G < 0 || S < 0 || in->num_nodes < 0 || in->num_entries < 0 || (!in->indices && S != G)) return GTOK_E_INVAL;
+  if (!in->node_slices || !in->edge_slices) return GTOK_E_INVAL;
+  if (in->num_nodes + G >= (1ll << 31)) return GTOK_E_TOO_LARGE;              // node offsets and row pointers are int32
+  if ((in->x && (!out->nattr || in->x_stride < 1)) || (in->edge_attr && (!out->eattr || in->edge_attr_stride < 1))) return GTOK_E_INVAL;
+  if (in->num_entries > 0 && (!in->src || !in->dst || !out->col || !out->eorder)) return GTOK_E_INVAL;
+  if (G > 0 && !out->rowptr) return GTOK_E_INVAL;
+  const CooWs w = coo_ws(G);
+  if (G > 0 && (!workspace || workspace_bytes < w.total || (reinterpret_cast<uintptr_t>(workspace) & 15u))) return GTOK_E_INVAL;
+  hipStream_t s = (hipStream_t)stream;
+  if (G == 0) {                                          // nothing to build: the pointers' one entry, and the totals
+    if (hipMemsetAsync(out->info, 0, 8 * sizeof(int32_t), s) != hipSuccess || hipMemsetAsync(out->node_ptr, 0, sizeof(int32_t), s) != hipSuccess ||
+        hipMemsetAsync(out->edge_ptr, 0, sizeof(int64_t), s) != hipSuccess)
+      return GTOK_E_LAUNCH;
+    if ((in->num_nodes || in->num_entries) && hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(out->info + kInfoStatus), GTOK_COO_BAD_TOTALS, 1, s) != hipSuccess)
+      return GTOK_E_LAUNCH;
+    return GTOK_OK;
+  }
+  uint8_t *ws = reinterpret_cast<uint8_t *>(workspace);
+  CooArgs a;
+  a.node_slices = in->node_slices; a.edge_slices = in->edge_slices; a.indices = in->indices; a.src = in->src; a.dst = in->dst;
+  a.x = out->nattr ? in->x : nullptr; a.ea = out->eattr ? in->edge_attr : nullptr;
+  a.x_stride = in->x_stride; a.ea_stride = in->edge_attr_stride; a.N = in->num_nodes; a.E = in->num_entries;
+  a.G = G; a.S = S; a.check = check != 0;
+  a.node_ptr = out->node_ptr; a.edge_ptr = out->edge_ptr; a.rowptr = out->rowptr; a.col = out->col; a.eorder = out->eorder;
+  a.nattr = in->x ? out->nattr : nullptr; a.eattr = in->edge_attr ? out->eattr : nullptr; a.info = out->info;
+  a.nsrc = reinterpret_cast<int64_t *>(ws + w.nsrc); a.esrc = reinterpret_cast<int64_t *>(ws + w.esrc);
+  a.gdeg = reinterpret_cast<int32_t *>(ws + w.gdeg); a.gneed = ws + w.gneed;
+  a.st_n = reinterpret_cast<int64_t *>(ws + w.st_n); a.st_e = reinterpret_cast<int64_t *>(ws + w.st_e);
+  a.ticket = reinterpret_cast<int *>(ws + w.ticket);
+  const int64_t nstates = 2ll * w.tiles;                 // st_n and st_e: one run
+  hipLaunchKernelGGL(csr_ws_init_kernel, dim3((unsigned)((nstates + 255) / 256)), dim3(256), 0, s, a.st_n, nstates, a.ticket, a.info);
+  hipLaunchKernelGGL(coo_ptr_kernel, dim3((unsigned)w.tiles), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(coo_build_kernel, dim3((unsigned)(((int64_t)G + 3) / 4)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(coo_fix_kernel, dim3((unsigned)(((int64_t)G + 255) / 256)), dim3(256), 0, s, a);
   return hipGetLastError() == hipSuccess ? GTOK_OK : GTOK_E_LAUNCH;
 }

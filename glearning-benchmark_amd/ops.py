@@ -152,6 +152,163 @@ def csr_check(batch: GraphBatch) -> Dict[str, int]:
     return dict(violations=v[0], max_degree=v[1], max_nodes=v[2], max_edges=v[3])
 
 
+COO_STATUS_TEXT = {_lib.COO_BAD_ENDPOINT: "edge endpoint outside [0, num_nodes)",
+                   _lib.COO_BAD_SLICES: "slices decrease or do not start at 0",
+                   _lib.COO_BAD_TOTALS: "the slices' totals differ from num_nodes / num_entries",
+                   _lib.COO_BAD_INDEX: "index outside [0, number of storage graphs)",
+                   _lib.COO_SORT_TOO_LARGE: f"an unsorted graph has more than {_lib.COO_SORT_NODES} nodes (too large for the device sort)"}
+
+
+class CooInputError(ValueError):
+    """gtok_csr_from_coo found its input damaged: `status` holds the GTOK_COO_* bits of info[6]."""
+
+    def __init__(self, status: int):
+        self.status = int(status)
+        super().__init__("csr_from_coo: " + "; ".join(t for b, t in COO_STATUS_TEXT.items() if self.status & b))
+
+
+def _type_column(a, dev, what: str):
+    """Column 0 of x / edge_attr ([n] or [n, k]); int64 device tensors are then read in place (with their stride), anything
+    else is converted and uploaded the way from_coo_device converts it."""
+    if a is None:
+        return None
+    t = torch.as_tensor(a)
+    if t.dim() == 0 or t.dim() > 2:
+        raise ValueError(f"{what} must be [n] or [n, k]")
+    if t.dim() == 2:
+        if t.shape[1] == 0:
+            raise ValueError(f"{what} has no column")
+        t = t[:, 0]
+    return t
+
+
+def _on_device(t, dev):
+    """A type column as gtok_coo takes it: (int64 tensor on dev, element stride)."""
+    if t is None:
+        return None, 0
+    if t.dtype != torch.int64 or t.device != dev or (t.numel() > 1 and t.stride(0) < 1):
+        t = t.to(dev, dtype=torch.int64).contiguous()
+    return t, max(1, int(t.stride(0)))
+
+
+def _coo_prepare(src, dst, node_slices, edge_slices, x, edge_attr, indices, num_nodes, num_entries, device):
+    """Argument checks and conversions of csr_from_coo (nothing is launched here): -> dict of device tensors and totals."""
+    if device is None:
+        device = src.device if torch.is_tensor(src) and src.device.type == "cuda" else "cuda"
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.GtokError(f"csr_from_coo: the build runs on the GPU (got device {dev}); the tokenizer has no CPU path")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    raw = {k: torch.as_tensor(v) for k, v in (("node_slices", node_slices), ("edge_slices", edge_slices))}
+    for k, t in raw.items():
+        if t.dim() != 1 or t.numel() < 1:
+            raise ValueError(f"{k} must be a 1-D array of S + 1 offsets")
+    if raw["node_slices"].numel() != raw["edge_slices"].numel():
+        raise ValueError("node_slices and edge_slices differ in length")
+    S = raw["node_slices"].numel() - 1
+    s_t, d_t = torch.as_tensor(src), torch.as_tensor(dst)
+    if s_t.dim() != 1 or d_t.dim() != 1 or s_t.numel() != d_t.numel():
+        raise ValueError("src and dst must be 1-D and of one length (the two rows of edge_index)")
+    idx = None
+    if indices is not None:
+        idx = torch.as_tensor(list(indices) if not torch.is_tensor(indices) and not isinstance(indices, np.ndarray) else indices)
+        if idx.dim() != 1:
+            raise ValueError("indices must be 1-D")
+        if idx.numel() and (idx.dtype.is_floating_point or idx.dtype == torch.bool):
+            raise ValueError("indices must be integers")
+    G = S if idx is None else int(idx.numel())
+    xa, ea = _type_column(x, dev, "x"), _type_column(edge_attr, dev, "edge_attr")
+    if ea is not None and ea.numel() != s_t.numel():
+        raise ValueError("edge_attr length does not match edge_index")
+    host = raw["node_slices"].device.type == "cpu" and raw["edge_slices"].device.type == "cpu"
+    if x is not None and host and xa.numel() != int(raw["node_slices"][-1]):
+        raise ValueError("x length does not match node_slices")
+    N, E = num_nodes, num_entries
+    if idx is None:
+        if E is None:
+            E = s_t.numel()
+        if N is None and xa is not None:
+            N = xa.numel()
+    if N is None or E is None:               # totals the inputs do not show: from host slices, else one read of two words
+        ns, es = raw["node_slices"].to(torch.int64), raw["edge_slices"].to(torch.int64)
+        if idx is not None:
+            ii = idx.to(ns.device, torch.int64)
+            inside = (ii >= 0) & (ii < S)                 # (an index outside the storage is the kernel's to report, counted as 0)
+            ii = torch.where(inside, ii, 0)
+            cnt = lambda sl: torch.where(inside, (sl[1:] - sl[:-1])[ii], 0).sum()
+            tot = torch.stack([cnt(ns), cnt(es)]) if S else torch.zeros(2, dtype=torch.int64)
+        else:
+            tot = torch.stack([ns[-1] - ns[0], es[-1] - es[0]])
+        tn, te = tot.tolist()
+        N = tn if N is None else N
+        E = te if E is None else E
+    N, E = int(N), int(E)
+    if N < 0 or E < 0:
+        raise ValueError("num_nodes and num_entries must be >= 0")
+    if N + G >= 2 ** 31:
+        raise ValueError("batch too large for int32 node offsets; shard it")
+    i64 = lambda t: t.reshape(-1).to(dev, dtype=torch.int64).contiguous()
+    (xa, xs), (ea, eas) = _on_device(xa, dev), _on_device(ea, dev)
+    return dict(dev=dev, G=G, S=S, N=N, E=E, src=i64(s_t), dst=i64(d_t), node_slices=i64(raw["node_slices"]),
+                edge_slices=i64(raw["edge_slices"]), indices=None if idx is None else i64(idx), x=xa, x_stride=xs, ea=ea, ea_stride=eas)
+
+
+def _coo_launch(p: dict, check_symmetric: bool):
+    """gtok_csr_from_coo on the current stream of p's device: -> (outputs dict, info int32 [8]) with no host read."""
+    dev, G, S, N, E = p["dev"], p["G"], p["S"], p["N"], p["E"]
+    i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
+    o = dict(node_ptr=i32(G + 1), edge_ptr=torch.empty(G + 1, dtype=torch.int64, device=dev), rowptr=i32(N + G), col=i32(E), eorder=i32(E),
+             nattr=None if p["x"] is None else torch.empty(N, dtype=torch.uint8, device=dev),
+             eattr=None if p["ea"] is None else torch.empty(E, dtype=torch.uint8, device=dev), info=i32(8))
+    L = lib()
+    ws = torch.empty(max(16, int(L.gtok_csr_from_coo_workspace(G, S))), dtype=torch.uint8, device=dev)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    cin = _lib.GtokCoo(G, S, N, E, ptr(p["node_slices"]), ptr(p["edge_slices"]), ptr(p["indices"]), ptr(p["src"]), ptr(p["dst"]),
+                       ptr(p["x"]), p["x_stride"], ptr(p["ea"]), p["ea_stride"])
+    cout = _lib.GtokCsrBuilt(*[ptr(o[n]) for n, _ in _lib.GtokCsrBuilt._fields_])
+    check(L.gtok_csr_from_coo(ctypes.byref(cin), int(bool(check_symmetric)), ctypes.byref(cout), ws.data_ptr(), ws.numel(), _stream(dev)),
+          "gtok_csr_from_coo")
+    return o, o["info"]
+
+
+def _coo_batch(o: dict, v, G: int, N: int, E: int, check_symmetric: bool) -> GraphBatch:
+    """The GraphBatch of gtok_csr_from_coo's outputs and its read-back info, filled as GraphBatch.from_coo_device fills it."""
+    flags = _lib.CSR_SIMPLE_SYMMETRIC if (check_symmetric and E and v[0] == 0) else 0
+    b = GraphBatch(G, v[2], v[3], o["node_ptr"], o["edge_ptr"], o["rowptr"], o["col"], o["eorder"] if v[7] else None, o["nattr"], o["eattr"],
+                   flags, v[4], v[5], v[1] if N else 0)
+    b.checked = bool(check_symmetric and E)
+    return b
+
+
+def _csr_from_coo(src, dst, node_slices, edge_slices, x=None, edge_attr=None, indices=None, check_symmetric=True,
+                  num_nodes=None, num_entries=None, device=None) -> Tuple[Optional[GraphBatch], int]:
+    """csr_from_coo without the raise: -> (batch, 0) or (None, status bits)."""
+    p = _coo_prepare(src, dst, node_slices, edge_slices, x, edge_attr, indices, num_nodes, num_entries, device)
+    o, info = _coo_launch(p, check_symmetric)
+    v = info.tolist()                                       # the one host read of the build
+    if v[6]:
+        return None, v[6]
+    return _coo_batch(o, v, p["G"], p["N"], p["E"], check_symmetric), 0
+
+
+def csr_from_coo(src, dst, node_slices, edge_slices, x=None, edge_attr=None, indices=None, check_symmetric: bool = True,
+                 num_nodes: Optional[int] = None, num_entries: Optional[int] = None, device=None) -> GraphBatch:
+    """The device GraphBatch of PyG collated storage, built by gtok_csr_from_coo (include/gtok.h): src / dst the two rows of
+    edge_index (LOCAL node ids), node_slices / edge_slices = slices['x'] / slices['edge_index'] ([S + 1]), x [n(, k)] and
+    edge_attr [E(, k)] optional (column 0 is the type), indices the storage graphs to take, in order (dataset._indices;
+    None = all).  The same arrays, flags and maxima as GraphBatch.from_coo on the same graphs, bit for bit; eorder is None
+    when every graph was already row-sorted.  Inputs of other dtypes or on the host are converted and uploaded.  The totals
+    of the batch come from the host side (x.shape[0], the entry count, host slices) or from num_nodes / num_entries; only
+    when neither shows them (device slices with indices, or without x) are they read back first.  One 32-byte read-back
+    otherwise.  A damaged input (endpoints outside the graph, decreasing slices, wrong totals, an index outside the storage,
+    an unsorted graph of more than COO_SORT_NODES nodes) raises CooInputError, a ValueError."""
+    b, status = _csr_from_coo(src, dst, node_slices, edge_slices, x, edge_attr, indices, check_symmetric, num_nodes, num_entries, device)
+    if status:
+        raise CooInputError(status)
+    return b
+
+
 def lane_sorted(batch: GraphBatch, verify: bool = False) -> Optional[GraphBatch]:
     """The copy of a device batch of small symmetric graphs that sent_lane_kernel walks fastest (made once per batch,
     kept on the batch object): graphs stored by descending expected walk length - nodes + leaves, a walk restarts once

@@ -297,6 +297,29 @@ _FRAG.impl("sent_packed", sent_packed, "CUDA")
 torch.library.register_fake("gtok::sent_packed", _sent_packed_fake, lib=_FRAG)
 
 
+@torch.library.custom_op("gtok::csr_from_coo", mutates_args=(), device_types="cuda")
+def csr_from_coo(src: Tensor, dst: Tensor, node_slices: Tensor, edge_slices: Tensor, x: Optional[Tensor], edge_attr: Optional[Tensor],
+                 indices: Optional[Tensor], num_nodes: int, num_entries: int, check: bool) -> List[Tensor]:
+    """The batched CSR of PyG collated storage (gtok_csr_from_coo; the arguments as ops.csr_from_coo, the totals of the batch
+    given): -> [node_ptr int32 [G+1], edge_ptr int64 [G+1], rowptr int32 [N+G], col int32 [E], eorder int32 [E], nattr uint8 [N]
+    (empty without x), eattr uint8 [E] (empty without edge_attr), info int32 [8] (include/gtok.h)].  Nothing is read back: the
+    call enqueues its launches and returns, so it can be captured into a CUDA graph; info[6] != 0 means the input was damaged
+    and the other outputs are undefined, info[7] == 0 that eorder is the identity."""
+    p = _ops._coo_prepare(src, dst, node_slices, edge_slices, x, edge_attr, indices, num_nodes, num_entries, src.device)
+    o, info = _ops._coo_launch(p, check)
+    e = lambda t: torch.empty(0, dtype=torch.uint8, device=src.device) if t is None else t
+    return [o["node_ptr"], o["edge_ptr"], o["rowptr"], o["col"], o["eorder"], e(o["nattr"]), e(o["eattr"]), info]
+
+
+@csr_from_coo.register_fake
+def _(src, dst, node_slices, edge_slices, x, edge_attr, indices, num_nodes, num_entries, check):
+    G = node_slices.shape[0] - 1 if indices is None else indices.shape[0]
+    e = lambda n, dt: src.new_empty((n,), dtype=dt)
+    return [e(G + 1, torch.int32), e(G + 1, torch.int64), e(num_nodes + G, torch.int32), e(num_entries, torch.int32),
+            e(num_entries, torch.int32), e(0 if x is None else num_nodes, torch.uint8), e(0 if edge_attr is None else num_entries, torch.uint8),
+            e(8, torch.int32)]
+
+
 @torch.library.custom_op("gtok::unpack_rows_at", mutates_args=(), device_types="cuda")
 def unpack_rows_at(packed: Tensor, row_start: Tensor, lens: Tensor, ld: int, pad_id: int, segment_rows: int, segment_stride: int,
                    u16: bool) -> Tensor:

@@ -42,6 +42,9 @@
  *   gtok_csr_lane_sort (no reference counterpart) the reordered copy of a small-graph batch that the lane-per-graph SENT kernel
  *                      walks fastest (graph_ids / unit_ptr / unit_info + the permuted arrays and their byte mirror), built on
  *                      the device: what a caller of trainer/train_agtt.py:246-250's tokenizer prepares once per split
+ *   gtok_csr_from_coo  the batched CSR from PyG collated storage (edge_index + slices['x'] / slices['edge_index'] + an optional
+ *                      subset, graph_token_dataset_autograph.py:336-348, zinc_dataset_autograph.py:51-73) built on the device:
+ *                      what GraphBatch.from_coo does on the host
  *   gtok_csr_pack8     (no reference counterpart) byte-packed mirror of the CSR index arrays of small-graph batches
  *   gtok_csr_adjbits   (no reference counterpart) adjacency bit-matrix mirror of batches of graphs with <= 256 nodes
  *   gtok_vocab_stats_text   the corpus pass of build_vocab_from_texts / the ZINC dynamic-token scan over arbitrary texts
@@ -230,6 +233,65 @@ typedef struct gtok_csr_sorted {
 int64_t gtok_csr_lane_sort_workspace(int32_t num_graphs);
 int gtok_csr_lane_sort(const gtok_csr *g, int32_t lds_budget, int32_t check, const gtok_csr_sorted *out, void *workspace,
                        int64_t workspace_bytes, void *stream);
+
+/* The batched CSR (gtok_csr's arrays) built on the device from PyG collated storage (ABI v7): `edge_index` int64 [2, sum E]
+ * with LOCAL node ids, slices['x'] / slices['edge_index'], optional x / edge_attr, optional subset `indices`
+ * (dataset._indices) - what graph_token_dataset_autograph.py:336-348 and zinc_dataset_autograph.py:51-73 hold.  Inputs
+ * (device memory, S = num_source_graphs, G = num_graphs):                                                              */
+typedef struct gtok_coo {
+  int32_t num_graphs;          /* G: graphs of the batch to build                                                  */
+  int32_t num_source_graphs;   /* S: graphs in the storage (must equal G when indices == NULL)                    */
+  int64_t num_nodes;           /* sum N of the batch to build (host-known: x.shape[0], slices[-1], the counts)     */
+  int64_t num_entries;         /* sum E of the batch to build                                                      */
+  const int64_t *node_slices;  /* [S + 1] slices['x']: graph s holds storage nodes [node_slices[s], node_slices[s+1]) */
+  const int64_t *edge_slices;  /* [S + 1] slices['edge_index']: likewise for the entries                           */
+  const int64_t *indices;      /* [G] storage graph of batch graph i; NULL = 0 .. S - 1                             */
+  const int64_t *src;          /* edge_index[0]: local row of every storage entry                                   */
+  const int64_t *dst;          /* edge_index[1]: local column                                                      */
+  const int64_t *x;            /* node type of storage node v at x[v * x_stride] (x[:, 0]); NULL = no node types    */
+  int64_t x_stride;            /* in elements, >= 1                                                                 */
+  const int64_t *edge_attr;    /* edge type of storage entry t at edge_attr[t * edge_attr_stride]; NULL = none      */
+  int64_t edge_attr_stride;
+} gtok_coo;
+/* Outputs (device memory, caller-allocated, N / E = num_nodes / num_entries):
+ *   node_ptr int32[G + 1], edge_ptr int64[G + 1], rowptr int32[N + G], col int32[E]: gtok_csr's layout; entries are
+ *       ordered by row with a STABLE sort (a row lists its entries in edge_index order), rowptr holds each graph's local row
+ *       starts and then E_g
+ *   eorder   int32[E]   always written: every entry's position in its graph's own edge list (the identity for a graph whose
+ *                       entries were already row-sorted; pass it as gtok_csr.eorder only when info[7] != 0)
+ *   nattr    uint8[N], eattr uint8[E]   when x / edge_attr are given: values 0..254 kept, everything else 255
+ *   info     int32[8]   [0] violations as gtok_csr_check counts them (0 <=> every graph simple and stored in both
+ *                       directions; 0 when check == 0), [1] max_degree, [2] max_nodes, [3] max_edges, [4] chunk_nodes,
+ *                       [5] chunk_edges (maxima over aligned groups of 64 graphs of the summed counts), [6] input status:
+ *                       GTOK_COO_* bits below, [7] 1 when some graph had to be sorted (eorder is not the identity)
+ * A damaged input raises bits of info[6] and never faults: the slices and indices are validated before anything is read
+ * through them and the scanned totals are compared with num_nodes / num_entries before anything is written with them
+ * (their bits leave every output but info undefined), PROVIDED the arrays hold as many elements as their slices say.
+ * An endpoint outside [0, N_g) leaves that graph's arrays undefined.  An unsorted graph of more than GTOK_COO_SORT_NODES
+ * nodes (its row cursors live in LDS; its entry count is not bounded) raises GTOK_COO_SORT_TOO_LARGE and its arrays are
+ * undefined.  The symmetry check uses a bit matrix in LDS for graphs of up to 256 nodes and gtok_csr_check's row scan for
+ * larger ones.  Everything is enqueued on `stream` (four launches) with no allocation and no host synchronisation, so the
+ * call can be captured into a hipGraph; the caller reads `info` back once.  `workspace`: gtok_csr_from_coo_workspace(G, S)
+ * bytes of device memory, 16-byte aligned, free again when the stream has run the call.                              */
+#define GTOK_COO_BAD_ENDPOINT   1   /* an endpoint outside [0, N_g)                                           */
+#define GTOK_COO_BAD_SLICES     2   /* slices that decrease, do not start at 0, or a graph of >= 2^31 entries */
+#define GTOK_COO_BAD_TOTALS     4   /* the scanned totals differ from num_nodes / num_entries                 */
+#define GTOK_COO_BAD_INDEX      8   /* an index outside [0, S)                                                 */
+#define GTOK_COO_SORT_TOO_LARGE 16  /* an unsorted graph of more than GTOK_COO_SORT_NODES nodes               */
+#define GTOK_COO_SORT_NODES 4096
+typedef struct gtok_csr_built {
+  int32_t *node_ptr;
+  int64_t *edge_ptr;
+  int32_t *rowptr;
+  int32_t *col;
+  int32_t *eorder;
+  uint8_t *nattr;
+  uint8_t *eattr;
+  int32_t *info;
+} gtok_csr_built;
+int64_t gtok_csr_from_coo_workspace(int32_t num_graphs, int32_t num_source_graphs);
+int gtok_csr_from_coo(const gtok_coo *in, int32_t check, const gtok_csr_built *out, void *workspace, int64_t workspace_bytes,
+                      void *stream);
 
 /* Adjacency bit-matrix mirror (see gtok_csr.adj_rows): rows = [sum N_g][words] uint64, planes = [G][8][words] uint64,
  * info = int32[1], zeroed by the caller, receives the largest closure degree.  words = 1, 2 or 4 with 64 * words >=
@@ -575,8 +637,8 @@ const char *gtok_ibtt_zinc_kernel_name(const gtok_csr *g);
  * mirrors - a binding checks it before passing structs; 3 adds the packed-row entry points; 4: gtok_sent_params carries
  * epoch_count, GTOK_SENT_U16, the strided / checked packed-row readers; 5 adds gtok_csr_check / gtok_csr_lane_sort -
  * structs unchanged; 6 adds gtok_sent_packed / GTOK_SENT_PACK_ONLY / gtok_unpack_rows_at / GTOK_E_UNSUPPORTED - structs
- * unchanged) and build target string ("gfx950").                     */
-#define GTOK_ABI_VERSION 6
+ * unchanged; 7 adds gtok_csr_from_coo - structs unchanged) and build target string ("gfx950").                     */
+#define GTOK_ABI_VERSION 7
 int gtok_version(void);
 const char *gtok_target(void);
 
