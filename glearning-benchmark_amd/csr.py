@@ -283,6 +283,10 @@ class GraphBatch:
             if ops.csr_check(out)["violations"] == 0:
                 out.flags |= CSR_SIMPLE_SYMMETRIC
             out.checked = True
+        elif check_symmetric and E:
+            # elsewhere (a CSR build, not tokenization): from_coo's numpy check, so the flag means what it means there
+            if _simple_symmetric(gid_e.cpu().numpy(), s.cpu().numpy(), d.cpu().numpy(), max_nodes):
+                out.flags |= CSR_SIMPLE_SYMMETRIC
         return out
 
     @staticmethod

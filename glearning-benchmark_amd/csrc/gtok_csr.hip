@@ -206,9 +206,15 @@ static void launch_csr_scan(CsrScanArgs a, const gtok_csr *g, hipStream_t s) {
     const int64_t r = (cn + 64 + 15) / 16 * 16, e = (ce + 15) / 16 * 16;
     if (4 * (r + (CHECK ? e : 0)) <= 150 * 1024) { a.cap_r = (int)r; a.cap_e = (int)e; }
   }
-  const size_t lds = (size_t)4 * (a.cap_r + (CHECK ? a.cap_e : 0));
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(csr_scan_kernel<CHECK>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  size_t lds = (size_t)4 * (a.cap_r + (CHECK ? a.cap_e : 0));
+  // the opt-in is to exactly what the launch takes (dynamic + the kernel's static LDS must fit the CU's 160 KB: asking for all
+  // 160 KB is refused); refused anyway, every group takes the general path
+  if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(csr_scan_kernel<CHECK>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)lds) != hipSuccess) {
+    (void)hipGetLastError();
+    a.cap_r = a.cap_e = 0;
+    lds = 0;
+  }
   hipLaunchKernelGGL(csr_scan_kernel<CHECK>, dim3((unsigned)(((int64_t)a.G + 255) / 256)), dim3(256), lds, s, a);
 }
 

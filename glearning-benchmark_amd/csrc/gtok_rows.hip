@@ -450,7 +450,9 @@ __global__ void __launch_bounds__(256) collate_packed_kernel(const void *__restr
   const int64_t src = index[b];
   int n = len[src];
   n = n < 0 ? 0 : (n > ld ? ld : n);
-  const E *__restrict__ row = reinterpret_cast<const E *>(packed) + (row_ptr ? row_ptr[src] : src * (int64_t)ld);
+  int64_t st = row_ptr ? row_ptr[src] : src * (int64_t)ld;
+  if (st < 0) { n = 0; st = 0; }                          // a row that did not fit its packed buffer (start -1): empty
+  const E *__restrict__ row = reinterpret_cast<const E *>(packed) + st;
   for (int i = lane; i < out_ld; i += kWave) {
     const bool in = i < n;
     out_x[(int64_t)b * out_ld + i] = in ? (int64_t)row[i] : (int64_t)pad_id;
@@ -510,7 +512,9 @@ __global__ void __launch_bounds__(256) collate_epoch_kernel(const void *__restri
   const int64_t src = order[r];
   int nn = len[src];
   nn = nn < 0 ? 0 : (nn > ld ? ld : nn);
-  const E *__restrict__ row = reinterpret_cast<const E *>(packed) + (row_ptr ? row_ptr[src] : src * (int64_t)ld);
+  int64_t st = row_ptr ? row_ptr[src] : src * (int64_t)ld;
+  if (st < 0) { nn = 0; st = 0; }                         // a row that did not fit its packed buffer (start -1): empty
+  const E *__restrict__ row = reinterpret_cast<const E *>(packed) + st;
   for (int i = lane; i < L; i += kWave) {
     const bool in = i < nn;
     out_x[at + i] = in ? (int64_t)row[i] : (int64_t)pad_id;
@@ -538,7 +542,9 @@ __global__ void __launch_bounds__(256) collate_batch_kernel(const BatchArgs a) {
   const int b = a.first + k;                              // row of the whole batch
   int n = a.len[src];
   n = n < 0 ? 0 : (n > a.ld ? a.ld : n);
-  const E *__restrict__ row = reinterpret_cast<const E *>(a.packed) + (a.row_ptr ? a.row_ptr[src] : src * (int64_t)a.ld);
+  int64_t st = a.row_ptr ? a.row_ptr[src] : src * (int64_t)a.ld;
+  if (st < 0) { n = 0; st = 0; }                          // a row that did not fit its packed buffer (start -1): empty
+  const E *__restrict__ row = reinterpret_cast<const E *>(a.packed) + st;
   for (int i = lane; i < a.out_ld; i += kWave) {
     const bool in = i < n;
     a.out_x[(int64_t)b * a.out_ld + i] = in ? (int64_t)row[i] : (int64_t)a.pad_id;
@@ -774,7 +780,8 @@ extern "C" int gtok_pack_rows_scan(const void *ids, int32_t src_bytes, int32_t l
   int sh = tpr_shift_for(ld);
   if (sh > 0) --sh;
   a.tpr_shift = sh;
-  a.fast = align == 8 && ((int64_t)ld * src_bytes) % 16 == 0 && ld % 8 == 0 && (reinterpret_cast<uintptr_t>(ids) & 15u) == 0 &&
+  // (the fast path stores a row's last piece whole: only a capacity of whole pieces keeps that store inside the buffer)
+  a.fast = align == 8 && ((int64_t)ld * src_bytes) % 16 == 0 && ld % 8 == 0 && capacity % 8 == 0 && (reinterpret_cast<uintptr_t>(ids) & 15u) == 0 &&
            (reinterpret_cast<uintptr_t>(packed) & 15u) == 0;
   a.chunk = (int)((tiles + 8ll * ncu - 1) / (8ll * ncu));
   if (a.chunk < 1) a.chunk = 1;

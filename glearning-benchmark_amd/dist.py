@@ -66,7 +66,8 @@ def gather_tokens(ids: torch.Tensor, ln: torch.Tensor, num_graphs: int, pad_id: 
     no slab): pass the slab width as `ld`.  as_packed=True (with packed=): the gathered rows are NOT re-padded - the call returns
     ((all_packed, row_start), len) with row_start[r] the absolute position of global row r in all_packed (what gtok_collate_packed /
     gtok_collate_batch / gtok_collate_epoch read in place through row_ptr = row_start, and gtok_unpack_rows_at re-pads if a slab is
-    wanted after all); rows a rank had to skip come back with length 0.
+    wanted after all); rows a rank had to skip (start -1, or a start whose row would end past `capacity`) come back with start -1
+    and length 0.
     rows_impl: the module providing row_offsets / pack_rows / unpack_rows (default: ops, i.e. the HIP kernels; the CPU
     tests of the collective pass the oracle's).  stats: a dict that receives the bytes each rank contributed."""
     if not (dist.is_available() and dist.is_initialized()) or (dist.get_world_size() == 1 and not force):
@@ -153,8 +154,10 @@ def _gather_prepacked(ids, ln, num_graphs, pad_id, packed, rows_impl, stats, wor
     if as_packed:
         # the rows stay where the collective put them: a row's absolute start = its rank's segment + its start there
         seg = torch.arange(world, dtype=torch.int64, device=dev).mul_(capacity).repeat_interleave(per)
-        skipped = all_start < 0
-        all_start = torch.where(skipped, all_start, all_start + seg)
+        # skipped: marked -1, or (a buffer some other caller filled) ending past its rank's segment - the collates that read
+        # these starts take no capacity
+        skipped = (all_start < 0) | (all_start + all_ln.clamp(0, ld) > capacity)
+        all_start = torch.where(skipped, -1, all_start + seg)
         all_ln = torch.where(skipped, torch.zeros_like(all_ln), all_ln)
         verdict = all_ext[:, per].max().to(torch.int32).reshape(1)
         if stats is not None:

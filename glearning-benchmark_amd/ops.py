@@ -319,7 +319,8 @@ def lane_sorted(batch: GraphBatch, verify: bool = False) -> Optional[GraphBatch]
     Built on the device by gtok_csr_lane_sort (counting sort, single-pass scans, the byte mirror in the same pass): a dozen
     small launches and ONE 32-byte read-back (the unit count and the LDS sizes of the launch).  verify=True: the batch's
     flags are not trusted - the same call checks GTOK_CSR_SIMPLE_SYMMETRIC on the device and sets it on `batch`
-    (None is returned when the batch turns out not to be simple and symmetric)."""
+    (None is returned when the batch turns out not to be simple and symmetric, or to hold a graph of more nodes or
+    entries than batch.max_nodes / batch.max_edges claim)."""
     if batch.lane_sorted is not None:
         return batch.lane_sorted
     if batch.col.device.type != "cuda" or batch.num_graphs == 0 or batch.max_nodes > 64 or batch.max_edges > 255 \
@@ -343,9 +344,11 @@ def lane_sorted(batch: GraphBatch, verify: bool = False) -> Optional[GraphBatch]
     cs = batch.c_struct()
     check(L.gtok_csr_lane_sort(ctypes.byref(cs), LANE_UNIT_LDS, int(verify), ctypes.byref(outs), ws.data_ptr(), ws.numel(), _stream(dev)),
           "gtok_csr_lane_sort")
-    viol, maxdeg, _, _, units, chunk_n, chunk_e, _ = o["info"].tolist()          # the one host read of the preparation
+    viol, maxdeg, maxn, maxe, units, chunk_n, chunk_e, _ = o["info"].tolist()          # the one host read of the preparation
     if verify:
-        if viol:
+        # (a claim below the measured maxima would give the lane kernel a graph its 64-bit visited sets cannot hold; the
+        # claims are <= 64 / 255 here, so the measured maxima are too)
+        if viol or maxn > batch.max_nodes or maxe > batch.max_edges:
             return None
         batch.flags |= _lib.CSR_SIMPLE_SYMMETRIC
         batch.max_degree = maxdeg
@@ -589,7 +592,9 @@ def sent(batch: GraphBatch, max_num_nodes: int, max_len: int, seed: int, epoch: 
             eb = 2 if u16 else 4
             check(lib().gtok_pack_rows_scan(ids.data_ptr(), eb, ld, ln.data_ptr(), K * G, 8, eb, packed.buf.data_ptr(), packed.capacity,
                                             ptr.data_ptr(), st.data_ptr(), _stream(dev)), "gtok_pack_rows_scan")
-            packed.row_start[:K * G].copy_(ptr[:-1])
+            # a row the scan skipped keeps its offset in ptr: it is marked -1 here, as the fused route marks it
+            skipped = ptr[:-1] + ln.clamp(0, ld) > packed.capacity
+            packed.row_start[:K * G].copy_(torch.where(skipped, -1, ptr[:-1]))
             packed.state[PACK_STATE_FILL:PACK_STATE_FILL + 1].copy_(ptr[-1:])
             packed.state[0:1].copy_(st.to(torch.int64) & 2)
     if not slab:

@@ -76,13 +76,24 @@ def _purge(cache: dict) -> None:
             del cache[key]
 
 
+def _refuse_understated(b: GraphBatch, r: dict) -> None:
+    """gtok_sent picks its kernel (and sizes its per-graph state) from max_nodes / max_edges: a claim below what gtok_csr_check
+    measured is refused before anything walks.  A claim above the measured maxima is legal."""
+    if r["max_nodes"] > b.max_nodes or r["max_edges"] > b.max_edges:
+        raise ValueError(f"max_nodes={b.max_nodes}, max_edges={b.max_edges} understate the batch: it holds graphs of up to "
+                         f"{r['max_nodes']} nodes and {r['max_edges']} entries")
+
+
 def _verify(b: GraphBatch) -> None:
-    """gtok_csr_check once per cached batch: what the flag claims is established on the device (one 32-byte read-back)."""
-    b.checked = True
+    """gtok_csr_check once per cached batch: what the flag claims is established on the device (one 32-byte read-back), and
+    maxima below the measured ones raise ValueError (the batch stays unchecked: a later call checks it again)."""
     if b.num_graphs == 0 or b.col.device.type != "cuda" or b.num_edges_total == 0:
+        b.checked = True
         return
     r = _ops.csr_check(b)
-    if r["violations"] == 0 and r["max_nodes"] <= b.max_nodes and r["max_edges"] <= b.max_edges:
+    _refuse_understated(b, r)
+    b.checked = True
+    if r["violations"] == 0:
         b.flags |= _lib.CSR_SIMPLE_SYMMETRIC
         b.max_degree = r["max_degree"]
 
@@ -134,7 +145,7 @@ def csr_prepare(node_ptr: Tensor, edge_ptr: Tensor, rowptr: Tensor, col: Tensor,
     graph_ids ... col8 and layout=layout.tolist() (prepared_args() does that): rows, lengths and RNG identities are those of
     the batch in dataset order.  A batch the lane-per-graph kernel does not take (more than 64 nodes / 255 entries per graph,
     or not simple and symmetric) comes back as empty arrays with layout[2] (num_units) == 0: keep calling with the
-    originals and flags = layout[0]."""
+    originals and flags = layout[0].  max_nodes / max_edges below the batch's measured maxima raise ValueError."""
     b = GraphBatch(int(node_ptr.numel()) - 1, max_nodes, max_edges, node_ptr, edge_ptr, rowptr, col, None, nattr, eattr)
     dev = col.device
     e = lambda dt: torch.empty(0, dtype=dt, device=dev)
@@ -143,8 +154,8 @@ def csr_prepare(node_ptr: Tensor, edge_ptr: Tensor, rowptr: Tensor, col: Tensor,
         flags = maxdeg = 0
         if b.num_graphs and b.num_edges_total:
             r = _ops.csr_check(b)
-            ok = r["violations"] == 0 and r["max_nodes"] <= max_nodes and r["max_edges"] <= max_edges
-            flags, maxdeg = (_lib.CSR_SIMPLE_SYMMETRIC if ok else 0), r["max_degree"]
+            _refuse_understated(b, r)
+            flags, maxdeg = (_lib.CSR_SIMPLE_SYMMETRIC if r["violations"] == 0 else 0), r["max_degree"]
         lay = torch.tensor([flags, maxdeg, 0, 0, 0, 0, 0], dtype=torch.int64)
         return [lay, e(torch.int32), e(torch.int64), e(torch.int32), e(torch.int32), e(torch.uint8), e(torch.uint8), e(torch.int32),
                 e(torch.int32), e(torch.int32), e(torch.uint8), e(torch.uint8)]

@@ -473,7 +473,9 @@ int gtok_parse_graph_text(const uint8_t *bytes, const int64_t *text_ptr, int32_t
  * gives - rows [s * segment_rows, (s + 1) * segment_rows) live in segment s: row r starts at
  * s * segment_stride + row_ptr[r] - row_ptr[s * segment_rows], with row_ptr = gtok_row_offsets over the gathered
  * lengths (same align).
- * gtok_collate_packed: gtok_collate reading the packed form (unsegmented) instead of the slab.
+ * gtok_collate_packed: gtok_collate reading the packed form (unsegmented) instead of the slab; a row whose row_ptr entry is
+ * negative (row_start -1: a row that did not fit its packed buffer) is collated as empty - gtok_collate_batch and
+ * gtok_collate_epoch do the same.
  * row_ptr == NULL (gtok_unpack_rows with segment_rows == 0, gtok_collate_packed): the STRIDED form - row r starts at
  * element r * ld of `packed` - i.e. a GTOK_SENT_U16 slab (or any [rows, ld] slab of 16- / 32-bit ids) read in place.
  * gtok_unpack_rows never reads beyond a segment: with segment_rows > 0 a row whose ids would end past segment_stride

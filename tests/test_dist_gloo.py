@@ -181,6 +181,66 @@ def _worker(rank, world, port, G, q):
         dist.destroy_process_group()
 
 
+def _hand_rows(rank, per, ld):
+    """rank's rows for the as_packed test: lengths 5..ld, 16-bit ids"""
+    rng = np.random.default_rng(40 + rank)
+    return rng.integers(5, ld + 1, per).astype(np.int32), rng.integers(0, 60000, (per, ld)).astype(np.uint16)
+
+
+def _skipped_rows_worker(rank, world, port, q):
+    """as_packed gather of PackedRows filled by hand (not by ops.sent): a start of -1 and a start whose row would end past the
+    rank's segment must both come back as start -1 and length 0 on every rank; the starts are checked before anything reads a row"""
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        G, ld, per = 20, 16, 10
+        ln, ids = _hand_rows(rank, per, ld)
+        ptr = orc.row_offsets(ln, ld, 8)
+        cap = int(ptr[-1])                               # (the same on both ranks: every row is 8 or 16 ids long)
+        cap = max(cap, int(orc.row_offsets(_hand_rows(1 - rank, per, ld)[0], ld, 8)[-1]))
+        pk = gtok.ops.PackedRows(per, cap, True, "cpu")
+        buf = np.full(pk.capacity, 0x7ABC, np.uint16)
+        for r in range(per):
+            buf[ptr[r]:ptr[r] + ln[r]] = ids[r, :ln[r]]
+        start = ptr[:-1].copy()
+        if rank == 0:
+            start[2] = pk.capacity - 4                   # would run into rank 1's segment
+        else:
+            start[3] = pk.capacity - 2                   # would run past the gathered buffer
+            start[6] = -1                                # marked skipped
+        pk.buf.copy_(torch.from_numpy(buf.view(np.int16)))
+        pk.row_start.copy_(torch.from_numpy(start))
+        pk.state.zero_()
+        pk.state[0] = 2
+        st = {}
+        (g_buf, g_start), g_ln = gtok.dist.gather_tokens(None, torch.from_numpy(ln), G, 5, compact=True, packed=pk, ld=ld, as_packed=True,
+                                                         rows_impl=_OracleRows, stats=st)
+        cap = pk.capacity
+        skipped = np.zeros(G, bool)
+        skipped[[2, per + 3, per + 6]] = True
+        rows = [_hand_rows(r, per, ld) for r in range(world)]
+        all_ln = np.concatenate([l for l, _ in rows])
+        all_ids = np.concatenate([i for _, i in rows])
+        all_ptr = np.concatenate([orc.row_offsets(l, ld, 8)[:-1] + r * cap for r, (l, _) in enumerate(rows)])
+        s, n = g_start.numpy(), g_ln.numpy()
+        ok = int(st["status"]) == 2 and g_buf.numel() == world * cap
+        # starts and lengths first: skipped rows are (-1, 0); every other row sits at its segment + its start and ends inside it
+        ok = ok and bool((s[skipped] == -1).all()) and bool((n[skipped] == 0).all())
+        ok = ok and np.array_equal(s[~skipped], all_ptr[~skipped]) and np.array_equal(n[~skipped], all_ln[~skipped])
+        ok = ok and bool((s[~skipped] + n[~skipped] <= np.repeat(np.arange(1, world + 1) * cap, per)[~skipped]).all())
+        if ok:                                           # only then are rows read through them
+            back = _OracleRows.unpack_rows_at(g_buf, g_start, g_ln, ld, 5, u16=True).numpy().view(np.uint16)
+            inside = np.arange(ld)[None, :] < all_ln[:, None]
+            ok = bool((back[skipped] == 5).all()) and np.array_equal(np.where(inside, back, 0)[~skipped], np.where(inside, all_ids, 0)[~skipped])
+        q.put((rank, bool(ok)))
+    except Exception:
+        import traceback
+        traceback.print_exc()
+        q.put((rank, False))
+    finally:
+        dist.destroy_process_group()
+
+
 def test_block_bounds():
     assert gtok.dist.block_bounds(10, 4) == [(0, 3), (3, 6), (6, 9), (9, 10)]
     assert gtok.dist.block_bounds(3, 4) == [(0, 1), (1, 2), (2, 3), (3, 3)]
@@ -193,6 +253,19 @@ def test_two_rank_shard_and_gather():
     port = _free_port()
     G = 101                                       # odd: the last block is short and gets padded for the gather
     procs = [ctx.Process(target=_worker, args=(r, 2, port, G, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    res = sorted(q.get(timeout=300) for _ in procs)
+    for p in procs:
+        p.join(timeout=60)
+    assert res == [(0, True), (1, True)]
+
+
+def test_as_packed_gather_marks_rows_that_lie_past_a_rank_s_buffer():
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_skipped_rows_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
     res = sorted(q.get(timeout=300) for _ in procs)

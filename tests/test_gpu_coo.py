@@ -101,6 +101,25 @@ def test_csr_from_coo_equals_the_host_builder():
             d.get("edge_attr") if labeled else None, device=DEV), k)
     untyped = _build(cases[0][0], labeled=False, check=False)
     assert untyped.nattr is None and untyped.eattr is None and untyped.flags == 0 and not untyped.checked
+    # x as [N, 3] int64 with the type in column 0 (read in place with stride 3; a non-contiguous view with stride 6; a transposed one
+    # with stride 1), edge_attr as [E, 2]; types -1, 255, 256 and 2**40 become 255 as in the host builder
+    d = gtok.synth.zinc_like(700, seed=45)
+    N, E = int(np.sum(d["node_counts"])), int(np.sum(d["edge_counts"]))
+    rng = np.random.default_rng(46)
+    odd = np.array([-1, 255, 256, 2 ** 40], np.int64)
+    xt, et = np.asarray(d["x"], np.int64).copy(), np.asarray(d["edge_attr"], np.int64).copy()
+    xt[rng.permutation(N)[:40]] = np.resize(odd, 40)
+    et[rng.permutation(E)[:40]] = np.resize(odd, 40)
+    h = gtok.GraphBatch.from_coo(d["node_counts"], d["edge_counts"], d["src"], d["dst"], xt, et)
+    assert int((h.nattr == 255).sum()) >= 40 and int((h.eattr == 255).sum()) >= 40
+    x3 = _dev(np.stack([xt, rng.integers(0, 9, N), rng.integers(-7, 7, N)], 1))
+    x6 = torch.cat([_dev(rng.integers(0, 300, (N, 3))), x3], 1)[:, 3:]
+    xT = x3.t().contiguous().t()
+    e2 = _dev(np.stack([et, rng.integers(0, 4, E)], 1))
+    assert x3.stride() == (3, 1) and x6.stride() == (6, 1) and not x6.is_contiguous() and xT.stride() == (1, N)
+    for xs, what in ((x3, "x [N, 3]"), (x6, "x [N, 3] view of [N, 6]"), (xT, "x [N, 3] transposed")):
+        g = gtok.ops.csr_from_coo(_dev(d["src"]), _dev(d["dst"]), _dev(_slices(d["node_counts"])), _dev(_slices(d["edge_counts"])), xs, e2)
+        _assert_same(h, g, what)
 
 
 def test_the_device_sort_bound():
@@ -186,6 +205,9 @@ def test_damaged_input_sets_status_bits_not_faults():
     s1 = d["src"].copy(); s1[7] = -1
     d1 = d["dst"].copy(); d1[int(es[5]) + 2] = int(d["node_counts"][5])
     assert status(src=s1) == lb.COO_BAD_ENDPOINT and status(dst=d1) == lb.COO_BAD_ENDPOINT
+    s2 = d["src"].copy(); s2[9] = 2 ** 32 + 1                       # endpoints that would wrap to a valid node in 32 bits
+    d2 = d["dst"].copy(); d2[int(es[7]) + 1] = -(2 ** 32)
+    assert status(src=s2) == lb.COO_BAD_ENDPOINT and status(dst=d2) == lb.COO_BAD_ENDPOINT
     bad_sl = es.copy(); bad_sl[10] = bad_sl[11] + 3
     assert status(esl=bad_sl) & lb.COO_BAD_SLICES
     assert status(N=int(ns[-1]) + 1) == lb.COO_BAD_TOTALS and status(E=int(es[-1]) - 1) == lb.COO_BAD_TOTALS
@@ -193,6 +215,7 @@ def test_damaged_input_sets_status_bits_not_faults():
     bad_nc = d["node_counts"].copy(); bad_nc[3] = -bad_nc[3]
     bad_ec = d["edge_counts"].copy(); bad_ec[4] += 1
     for args in ((d["node_counts"], d["edge_counts"], s1, d["dst"]), (d["node_counts"], d["edge_counts"], d["src"], d1),
+                 (d["node_counts"], d["edge_counts"], s2, d["dst"]), (d["node_counts"], d["edge_counts"], d["src"], d2),
                  (bad_nc, d["edge_counts"], d["src"], d["dst"]), (d["node_counts"], bad_ec, d["src"], d["dst"])):
         errs = []
         for builder in ("torch", "auto"):

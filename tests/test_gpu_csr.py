@@ -247,3 +247,58 @@ def test_lane_kernel_through_bare_ctypes_without_ops_py():
     assert L.gtok_csr_lane_sort(ctypes.byref(big), 0, 0, ctypes.byref(outs), ws.data_ptr(), ws.numel(), stream) == -2  # GTOK_E_TOO_LARGE
     assert L.gtok_csr_check(ctypes.byref(srt), o["info"].data_ptr(), stream) == -1                                      # a reordered batch
     assert L.gtok_csr_check(None, o["info"].data_ptr(), stream) == -1
+
+
+def _with_ring(d, n_ring):
+    """d (simple symmetric molecules) + one ring of n_ring nodes, both directions listed, row-sorted, typed as carbon / single."""
+    i = np.arange(n_ring)
+    pairs = np.stack([np.minimum(i, (i + 1) % n_ring), np.maximum(i, (i + 1) % n_ring)], 1)
+    s = np.concatenate([pairs[:, 0], pairs[:, 1]]); t = np.concatenate([pairs[:, 1], pairs[:, 0]])
+    o = np.lexsort((t, s))
+    return dict(node_counts=np.append(d["node_counts"], n_ring), edge_counts=np.append(d["edge_counts"], s.size),
+                src=np.concatenate([d["src"], s[o]]), dst=np.concatenate([d["dst"], t[o]]),
+                x=np.concatenate([d["x"], np.zeros(n_ring, np.int64)]), edge_attr=np.concatenate([d["edge_attr"], np.ones(s.size, np.int64)]))
+
+
+def test_understated_maxima_are_refused_before_any_walk():
+    """A batch of molecules (<= 64 nodes, <= 255 entries) plus one ring of 100 nodes (200 entries: still bytes) under claims below
+    its measured maxima: lane_sorted(verify=True) gives no layout, csr_prepare and the raw-tensor SENT ops raise ValueError naming the
+    measured maxima - all before anything walks.  With its true maxima (or larger claims) the same corpus tokenizes as the oracle does."""
+    d = _with_ring(gtok.synth.zinc_like(500, seed=95), 100)
+    host, coo = both(d)
+    assert host.flags & gtok._lib.CSR_SIMPLE_SYMMETRIC and (host.max_nodes, host.max_edges) == (100, 200)
+    assert int(np.max(d["node_counts"][:-1])) <= 64 and int(np.max(d["edge_counts"][:-1])) <= 255
+    T = _tensors(host)
+    args = dict(query=None, max_num_nodes=128, max_len=1024, ld=1024, seed=6, epoch=1, labeled=True, num_node_types=9, num_edge_types=4,
+                remap_zinc=True, pad_id=5, graph_base=0)
+    bare = lambda mn, me: gtok.GraphBatch(host.num_graphs, mn, me, T["node_ptr"], T["edge_ptr"], T["rowptr"], T["col"], None, T["nattr"], T["eattr"])
+    for mn, me in ((64, 200), (100, 150), (64, 150)):
+        b = bare(mn, me)
+        assert gtok.ops.lane_sorted(b, verify=True) is None and not (b.flags & gtok._lib.CSR_SIMPLE_SYMMETRIC), (mn, me)
+        with pytest.raises(ValueError, match="100 nodes and 200 entries"):
+            torch.ops.gtok.csr_prepare(T["node_ptr"], T["edge_ptr"], T["rowptr"], T["col"], T["nattr"], T["eattr"], mn, me)
+        with pytest.raises(ValueError, match="100 nodes and 200 entries"):
+            gtok.torch_ops._sent_batch(T["node_ptr"], T["edge_ptr"], T["rowptr"], T["col"], T["nattr"], T["eattr"], mn, me,
+                                       None, None, None, None, None, None, None, None, None)
+    # only now through the ops that would walk: they raise, and no launch was set up
+    for mn, me in ((64, 200), (100, 150), (64, 150)):
+        before = gtok.ops._LAST_SENT
+        with pytest.raises(ValueError, match="understate"):
+            torch.ops.gtok.sent(**T, max_nodes=mn, max_edges=me, **args)
+        with pytest.raises(ValueError, match="understate"):
+            torch.ops.gtok.sent_packed(T["node_ptr"], T["edge_ptr"], T["rowptr"], T["col"], T["nattr"], T["eattr"], None, mn, me, 128, 1024,
+                                       1024, 6, 1, 1, True, 9, 4, True, 5, 0, True, 1 << 16)
+        assert gtok.ops._LAST_SENT is before
+    # the control: true maxima, and claims above them, tokenize as the oracle does
+    ref, rln = orc.sent(coo, 128, 1024, 6, 1, ld=1024, **ZKW)
+    for mn, me in ((100, 200), (128, 255)):
+        lay = torch.ops.gtok.csr_prepare(T["node_ptr"], T["edge_ptr"], T["rowptr"], T["col"], T["nattr"], T["eattr"], mn, me)[0].tolist()
+        assert lay[0] == gtok._lib.CSR_SIMPLE_SYMMETRIC and lay[2] == 0                # simple and symmetric; too large for the lane kernel
+        ids, ln = torch.ops.gtok.sent(**T, max_nodes=mn, max_edges=me, **args)
+        assert np.array_equal(ln.cpu().numpy(), rln) and np.array_equal(ids.cpu().numpy(), ref), (mn, me)
+    # a claim above the molecules' own maxima still gets the lane layout
+    mol, mcoo = both(gtok.synth.zinc_like(500, seed=95))
+    M = _tensors(mol)
+    sb = gtok.ops.lane_sorted(gtok.GraphBatch(mol.num_graphs, 64, 255, M["node_ptr"], M["edge_ptr"], M["rowptr"], M["col"], None, M["nattr"],
+                                              M["eattr"]), verify=True)
+    assert sb is not None and sb.flags & gtok._lib.CSR_SIMPLE_SYMMETRIC

@@ -11,6 +11,7 @@ from _util import both, edge_case_graphs, gtok, orc
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
+ZKW = dict(labeled=True, num_node_types=9, num_edge_types=4, remap_zinc=True)
 
 
 def _pin(monkeypatch, pin):
@@ -615,3 +616,97 @@ def test_sent_packed_with_a_slab_too_narrow_for_some_rows(u16):
     ref, rln = orc.sent(coo, 37, 1024, 4, 1, ld=ld, **kw)
     got = slab.cpu().numpy()
     assert np.array_equal(got.view(np.uint16).astype(np.int32) if u16 else got, ref) and np.array_equal(sln.cpu().numpy(), rln)
+
+
+def _fallback_case(pin, monkeypatch):
+    """(batch, oracle corpus, walk arguments, kernel name) of a batch that another kernel than sent_lane_kernel walks"""
+    if pin == "reg":                      # the natural route of a split of a few thousand molecules
+        monkeypatch.delenv("GTOK_SENT_KERNEL", raising=False)
+        d, labeled, kw = gtok.synth.zinc_like(3000, seed=87), True, dict(remap_zinc=True, num_node_types=9, num_edge_types=4)
+    else:
+        _pin(monkeypatch, pin)
+        if pin == "lds":
+            d, labeled, kw = gtok.synth.zinc_like(1200, seed=88), True, dict(remap_zinc=True, num_node_types=9, num_edge_types=4)
+        else:
+            d, labeled, kw = gtok.synth.er_batch(300, seed=89, min_nodes=10, max_nodes=60), False, {}
+    batch, coo = both(d, labeled)
+    return batch.to(DEV), coo, dict(kw, labeled=labeled), f"sent_{pin}_kernel"
+
+
+@pytest.mark.parametrize("pin", ["reg", "lds", "blane"])
+@pytest.mark.parametrize("u16", [True, False])
+@pytest.mark.parametrize("K", [1, 3])
+def test_sent_packed_fallback_marks_rows_that_did_not_fit(pin, u16, K, monkeypatch):
+    """ops.sent(..., packed=) where another kernel walks (gtok_sent + gtok_pack_rows_scan) into a buffer of about half the rows'
+    total: a row the scan skipped has row_start -1, exactly as on the fused route, so that no reader goes past the buffer."""
+    b, coo, kw, name = _fallback_case(pin, monkeypatch)
+    G, nn, max_len = b.num_graphs, 60, 512
+    ld = gtok.ops.sent_safe_ld(b, kw["labeled"], max_len)
+    full, fln = gtok.ops.sent(b, nn, max_len, seed=2, epoch=3, ld=ld, epochs=K, u16=u16, **kw)
+    full, fln = full.reshape(-1, ld), fln.reshape(-1)
+    need = int(((fln.clamp(0, ld) + 7) // 8 * 8).sum())
+    cap = need // 2 // 8 * 8
+    pk = gtok.ops.PackedRows(K * G, cap, u16, DEV)
+    assert pk.capacity == cap
+    pk.buf.fill_(0x7777)
+    ids, ln = gtok.ops.sent(b, nn, max_len, seed=2, epoch=3, ld=ld, pad=False, epochs=K, u16=u16, packed=pk, **kw)
+    assert pk.fused is False and gtok.ops.last_sent_kernel().startswith(name) and int(pk.status()) == 2
+    # the starts first, against the host restatement of the one-pass pack (8-id alignment, dataset order)
+    lnh = ln.reshape(-1).cpu().numpy()
+    assert np.array_equal(lnh, fln.cpu().numpy())                  # ln keeps the true lengths, as on the fused route
+    ptr = orc.row_offsets(lnh, ld, 8)
+    n = np.clip(lnh, 0, ld)
+    skip = ptr[:-1] + n > cap
+    st = pk.row_start[:K * G].cpu().numpy()
+    assert skip.any() and (~skip).any()
+    assert np.array_equal(st == -1, skip) and np.array_equal(st[~skip], ptr[:-1][~skip])
+    assert (st[~skip] + n[~skip] <= cap).all(), "a kept row ends inside the buffer"
+    # kept rows are the oracle's
+    buf = pk.buf.cpu().numpy()
+    buf = buf.view(np.uint16) if u16 else buf
+    cols = np.arange(ld)[None, :]
+    for e in sorted({0, K - 1}):
+        ref, rln = orc.sent(coo, nn, max_len, 2, 3 + e, ld=ld, **kw)
+        rows = slice(e * G, (e + 1) * G)
+        assert np.array_equal(lnh[rows], rln)
+        got = buf[np.clip(st[rows][:, None] + cols, 0, buf.size - 1)]
+        inside = (cols < rln[:, None]) & ~skip[rows][:, None]
+        assert np.array_equal(np.where(inside, got, 0), np.where(inside, ref, 0)), e
+    # the readers: unpack_rows_at pads the skipped rows and says so; collate_packed reads them as empty
+    stt = torch.zeros(1, dtype=torch.int32, device=DEV)
+    back = gtok.ops.unpack_rows_at(pk.buf, pk.row_start, ln.reshape(-1), ld, 5, status=stt, u16=u16)
+    kept = torch.from_numpy(~skip).to(DEV)
+    assert torch.equal(back[kept], full[kept]) and bool((back[~kept] == 5).all()) and int(stt.item()) == 2
+    idx = torch.cat([torch.nonzero(~kept)[:40, 0], torch.nonzero(kept)[:200, 0]])
+    idx = idx[torch.randperm(idx.numel(), generator=torch.Generator().manual_seed(K)).to(DEV)]
+    ln0 = torch.where(kept, ln.reshape(-1), 0)
+    lmax = int(ln0[idx].max())
+    X, A = gtok.ops.collate_packed(pk.buf, pk.row_start, ln.reshape(-1), ld, idx, 5, lmax)
+    rX, rA = gtok.ops.collate_packed(full, None, ln0, ld, idx, 5, lmax)
+    assert torch.equal(X, rX) and torch.equal(A, rA)
+
+
+def test_sent_packed_fallback_through_the_torch_custom_op_marks_rows_that_did_not_fit():
+    """torch.ops.gtok.sent_packed on a batch another kernel walks (the shape of test_sent_packed_through_the_torch_custom_ops) with
+    a capacity of about half the rows: status 2, skipped rows start at -1, kept rows end inside the buffer and re-pad to the slab."""
+    G, K, ld = 700, 3, 176
+    d = gtok.synth.zinc_like(G, seed=56)
+    batch, coo = both(d)
+    b = batch.to(DEV)
+    full, fln = gtok.ops.sent(b, 37, 1024, seed=9, epoch=2, ld=ld, epochs=K, u16=True, **ZKW)
+    need = int(((fln.reshape(-1).clamp(0, ld) + 7) // 8 * 8).sum())
+    cap = need // 2 // 8 * 8
+    args = (b.node_ptr, b.edge_ptr, b.rowptr, b.col, b.nattr, b.eattr, None, b.max_nodes, b.max_edges, 37, 1024, ld, 9, 2, K, True, 9, 4,
+            True, 5, 0, True, cap)
+    ln, packed, start, state = torch.ops.gtok.sent_packed(*args)
+    assert gtok.ops.last_sent_kernel() != "sent_lane_kernel" and state.tolist() == [need, 2] and packed.numel() == cap
+    lnh, st = ln.cpu().numpy(), start.cpu().numpy()
+    ptr = orc.row_offsets(lnh, ld, 8)
+    n = np.clip(lnh, 0, ld)
+    skip = ptr[:-1] + n > cap
+    assert skip.any() and np.array_equal(st == -1, skip) and np.array_equal(st[~skip], ptr[:-1][~skip]) and (st[~skip] + n[~skip] <= cap).all()
+    slab = torch.ops.gtok.unpack_rows_at(packed, start, ln, ld, 5, 0, 0, True)
+    kept = torch.from_numpy(~skip).to(DEV)
+    assert torch.equal(slab[kept], full.reshape(-1, ld)[kept]) and bool((slab[~kept] == 5).all())
+    ref, rln = orc.sent(coo, 37, 1024, 9, 2, ld=ld, **ZKW)
+    assert np.array_equal(lnh[:G], rln) and np.array_equal(_u(slab[:G])[~skip[:G]], ref[~skip[:G]])

@@ -359,3 +359,112 @@ def test_pack_rows_scan_with_several_tiles_per_ticket_and_large_host_batches(mon
     assert torch.equal(X, Xr) and torch.equal(A, Ar) and torch.equal(Y, y[torch.from_numpy(idx).to(DEV)])
     yl = torch.arange(5000, dtype=torch.int64, device=DEV) * 3
     assert torch.equal(gtok.ops.collate_batch(d16, None, d_ln, 40, idx[:5], 5, 16, yl)[2], yl[torch.from_numpy(idx[:5]).to(DEV)])
+
+
+@pytest.mark.parametrize("ld,align", [(48, 8), (13, 1)])
+def test_pack_rows_scan_never_writes_past_capacity(ld, align):
+    """gtok_pack_rows_scan into the first `cap` elements of a larger buffer filled with a sentinel, at capacities that are not
+    whole 8-id pieces (the fast path - align 8, ld % 8 == 0 - stores a row's last piece whole): nothing beyond `cap` changes, the
+    rows that fit are the slab's, status bit 1 says exactly whether a row was skipped, row_ptr is the host restatement's."""
+    import ctypes
+    rows = 700
+    ids, ln = _slab(rows, ld, seed=ld * 7 + align)
+    want_ptr = orc.row_offsets(ln, ld, align)
+    total, n = int(want_ptr[-1]), np.clip(ln, 0, ld)
+    r5 = int(np.nonzero((n % 8 != 0) & ((want_ptr[:-1] + n) % 8 != 0))[0][3])      # a row whose length is not a multiple of 8
+    row_end = int(want_ptr[r5] + n[r5])
+    stream = torch.cuda.current_stream().cuda_stream
+    L = gtok._lib.lib()
+    d_ln = torch.from_numpy(ln).to(DEV)
+    d_ids = torch.from_numpy(ids).to(DEV)
+    for src in (d_ids, d_ids.to(torch.int16)):
+        sb = src.element_size()
+        for eb in ((2, 4) if sb == 4 else (2, 4, 8)):
+            dt = {2: torch.int16, 4: torch.int32, 8: torch.int64}[eb]
+            for cap in (row_end, total - 1, total - 5, total + 3):
+                big = torch.full((cap + 64,), 0x3C3C, dtype=dt, device=DEV)
+                ptr = torch.empty(rows + 1, dtype=torch.int64, device=DEV)
+                st = torch.full((1,), -1, dtype=torch.int32, device=DEV)
+                assert L.gtok_pack_rows_scan(src.data_ptr(), sb, ld, d_ln.data_ptr(), rows, align, eb, big.data_ptr(), cap, ptr.data_ptr(),
+                                             st.data_ptr(), stream) == 0
+                torch.cuda.synchronize()
+                what = (src.dtype, eb, cap)
+                assert bool((big[cap:] == 0x3C3C).all()), ("written past capacity", what)
+                assert np.array_equal(ptr.cpu().numpy(), want_ptr), what
+                fits = want_ptr[:-1] + n <= cap
+                assert int(st.item()) == (0 if fits.all() else 2), (int(st.item()), what)
+                got = big.cpu().numpy()
+                got = got.view(np.uint16) if eb == 2 else got
+                for r in np.nonzero(fits)[0]:
+                    assert np.array_equal(got[want_ptr[r]:want_ptr[r] + n[r]].astype(np.int64), ids[r, :n[r]]), (r, what)
+
+
+def test_sent_packed_into_an_odd_capacity_never_writes_past_it():
+    """gtok_sent_packed through the C ABI into a guarded view of an odd capacity (its regions are whole 8-id pieces: rounded down)."""
+    import ctypes
+    G, ld = 30016, 176
+    d = gtok.synth.zinc_like(G, seed=93)
+    b = gtok.GraphBatch.from_coo(d["node_counts"], d["edge_counts"], d["src"], d["dst"], d["x"], d["edge_attr"]).to(DEV)
+    kw = dict(labeled=True, num_node_types=9, num_edge_types=4, remap_zinc=True)
+    full, fln = gtok.ops.sent(b, 37, 1024, seed=4, ld=ld, u16=True, **kw)            # also builds the reordered copy
+    need = int(((fln.clamp(0, ld) + 7) // 8 * 8).sum())
+    L = gtok._lib.lib()
+    cs = b.lane_sorted.c_struct()
+    p = gtok._lib.GtokSentParams(37, 1, 9, 4, 1024, 1, 5, gtok._lib.SENT_U16 | gtok._lib.SENT_NO_PAD, 4, 0, 0, None, 1, 0)
+    stream = torch.cuda.current_stream().cuda_stream
+    for cap in (need + 5, need // 2 + 3):
+        big = torch.full((cap + 64,), 0x3C3C, dtype=torch.int16, device=DEV)
+        ids = torch.empty((G, ld), dtype=torch.int16, device=DEV)
+        ln = torch.empty(G, dtype=torch.int32, device=DEV)
+        start = torch.empty(G, dtype=torch.int64, device=DEV)
+        state = torch.zeros(gtok.ops.PACK_STATE_WORDS, dtype=torch.int64, device=DEV)
+        assert L.gtok_sent_packed(ctypes.byref(cs), ctypes.byref(p), ids.data_ptr(), ld, ln.data_ptr(), big.data_ptr(), cap, start.data_ptr(),
+                                  state.data_ptr(), stream) == 0
+        torch.cuda.synchronize()
+        assert bool((big[cap:] == 0x3C3C).all()), cap
+        assert torch.equal(ln, fln)
+        s, n = start.cpu().numpy(), fln.clamp(0, ld).cpu().numpy()
+        assert ((s < 0) | (s + n <= cap)).all() and bool(s.min() >= 0) == (int(state[0]) == 0), cap
+        back = gtok.ops.unpack_rows_at(big, start, ln, ld, 5, u16=True)
+        kept = torch.from_numpy(s >= 0).to(DEV)
+        assert torch.equal(back[kept], full[kept]) and bool((back[~kept] == 5).all())
+
+
+def test_as_packed_gather_over_rccl_marks_rows_the_fallback_skipped():
+    """dist.gather_tokens(None, ..., as_packed=True) through a one-rank `nccl` group, fed by the undersized buffer of the non-fused
+    route: the skipped rows come back with start -1 and length 0 - checked before anything is collated - and the collate over the
+    gathered rows is the slab's with those rows empty."""
+    import socket
+    import torch.distributed as tdist
+    G, ld = 3000, 176
+    d = gtok.synth.zinc_like(G, seed=94)
+    batch, _ = both(d)
+    b = batch.to(DEV)
+    kw = dict(labeled=True, num_node_types=9, num_edge_types=4, remap_zinc=True)
+    full, fln = gtok.ops.sent(b, 37, 1024, seed=8, ld=ld, u16=True, **kw)
+    need = int(((fln.clamp(0, ld) + 7) // 8 * 8).sum())
+    pk = gtok.ops.PackedRows(G, need // 2 // 8 * 8, True, DEV)
+    _, ln = gtok.ops.sent(b, 37, 1024, seed=8, ld=ld, u16=True, packed=pk, slab=False, **kw)
+    assert pk.fused is False and int(pk.status()) == 2
+    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    tdist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device(DEV))
+    try:
+        st = {}
+        (g_buf, g_start), g_ln = gtok.dist.gather_tokens(None, ln, G, 5, force=True, compact=True, packed=pk, ld=ld, as_packed=True, stats=st)
+    finally:
+        tdist.destroy_process_group()
+    ptr = orc.row_offsets(fln.cpu().numpy(), ld, 8)
+    skip = ptr[:-1] + np.clip(fln.cpu().numpy(), 0, ld) > pk.capacity
+    gs, gl = g_start.cpu().numpy(), g_ln.cpu().numpy()
+    assert int(st["status"]) == 2 and skip.any() and (~skip).any()
+    assert (gs[skip] == -1).all() and (gl[skip] == 0).all()
+    assert np.array_equal(gs[~skip], ptr[:-1][~skip]) and np.array_equal(gl[~skip], fln.cpu().numpy()[~skip])
+    assert (gs[~skip] + gl[~skip] <= pk.capacity).all()
+    kept = torch.from_numpy(~skip).to(DEV)
+    idx = torch.randperm(G, generator=torch.Generator().manual_seed(2))[:300].to(DEV)
+    ln0 = torch.where(kept, fln, 0)
+    lmax = int(ln0[idx].max())
+    X, A = gtok.ops.collate_packed(g_buf, g_start, g_ln, ld, idx, 5, lmax)
+    rX, rA = gtok.ops.collate_packed(full, None, ln0, ld, idx, 5, lmax)
+    assert torch.equal(X, rX) and torch.equal(A, rA)

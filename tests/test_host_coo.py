@@ -46,3 +46,26 @@ def test_csr_from_coo_refuses_a_cpu_build():
         gtok.ops.csr_from_coo(np.zeros(1, np.int64), np.zeros(1, np.int64), np.array([0, 1]), np.array([0, 1]), device="cpu")
     with pytest.raises(ValueError, match="builder"):
         gtok.GraphBatch.from_coo_device([1], [0], [], [], device="cpu", builder="hip")
+
+
+def test_from_coo_device_off_the_gpu_sets_the_flags_from_coo_sets():
+    """check_symmetric=True on a non-CUDA device: the same GTOK_CSR_SIMPLE_SYMMETRIC verdict, and the same `checked`, as
+    from_coo - on a clean corpus, one with a self loop and one with an entry whose reverse is missing."""
+    d = gtok.synth.zinc_like(300, seed=7)
+    ep = np.concatenate([[0], np.cumsum(d["edge_counts"])])
+    k = int(ep[17]) + 3                                    # an entry of graph 17
+    loop = dict(d, dst=d["dst"].copy())
+    loop["dst"][k] = loop["src"][k]
+    ec = d["edge_counts"].copy(); ec[17] -= 1
+    missing = dict(d, src=np.delete(d["src"], k), dst=np.delete(d["dst"], k), edge_attr=np.delete(d["edge_attr"], k), edge_counts=ec)
+    verdicts = []
+    for c in (d, loop, missing):
+        args = (c["node_counts"], c["edge_counts"], c["src"], c["dst"], c["x"], c["edge_attr"])
+        h = gtok.GraphBatch.from_coo(*args, check_symmetric=True)
+        b = gtok.GraphBatch.from_coo_device(*args, device="cpu", builder="torch", check_symmetric=True)
+        assert (b.flags, b.checked) == (h.flags, h.checked)
+        assert torch.equal(b.rowptr, h.rowptr) and torch.equal(b.col, h.col)
+        verdicts.append(bool(h.flags & gtok._lib.CSR_SIMPLE_SYMMETRIC))
+    assert verdicts == [True, False, False]
+    # check_symmetric=False: no verdict either way
+    assert gtok.GraphBatch.from_coo_device(*args[:4], device="cpu", builder="torch", check_symmetric=False).flags == 0
