@@ -43,6 +43,7 @@ CSR_SIMPLE_SYMMETRIC = 1
 SENT_NO_PAD = 1
 SENT_U16 = 2
 SENT_PACK_ONLY = 4
+SENT_PACK_U8 = 8
 
 
 class GtokCsrSorted(ctypes.Structure):
@@ -193,7 +194,7 @@ _lib = None
 _lib_version = 0
 
 
-ABI_VERSION = 7     # include/gtok.h: GTOK_ABI_VERSION
+ABI_VERSION = 8     # include/gtok.h: GTOK_ABI_VERSION
 
 
 def lib() -> ctypes.CDLL:

@@ -4,7 +4,7 @@
 // padding and every id fits 16 bits, so the copies that leave the GPU - the RCCL all-gather of BASELINE config 4
 // (trainer/train_agtt.py:602-607 needs the rows in dataset order on every rank) and the D2H copy behind
 // TokenizedGraphDataset.__getitem__ (trainer/train_agtt.py:246-273) - move the packed form: row r's
-// n_r = min(len[r], ld) ids, 16 or 32 bits each, contiguous from element row_ptr[r].  Pure data movement: HBM-bound,
+// n_r = min(len[r], ld) ids, 8, 16 or 32 bits each, contiguous from element row_ptr[r].  Pure data movement: HBM-bound,
 // no LDS, every access a 16-byte vector when the row starts allow it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -129,11 +129,62 @@ struct RowsArgs {
   int64_t segment_stride, capacity;   // pack: elements `packed` can hold; unpack: elements it holds (0 = unknown)
 };
 
-// S = source id type (int32_t slab, or uint16_t: a GTOK_SENT_U16 slab), E = packed id type (uint16_t, int32_t or
-// int64_t).  A thread owns pieces of 8 consecutive ids of one row: 16-byte loads and stores; 1 << tpr_shift threads
-// share a row, 256 >> tpr_shift rows a workgroup.
+// ---- one byte per id (E = uint8_t): a piece is 16 consecutive ids - two 16-byte loads of a 16-bit slab, four of an int32
+// slab, ONE 16-byte store.  The ids are ORed into `wide` whole: a bit above the low eight is an id that does not fit.
+template <typename S>
+__device__ __forceinline__ void load_ids16(const S *__restrict__ src, uint32_t (&t)[16]) {
+  if (sizeof(S) == 4) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint4 p = *reinterpret_cast<const uint4 *>(src + 4 * k);
+      t[4 * k] = p.x; t[4 * k + 1] = p.y; t[4 * k + 2] = p.z; t[4 * k + 3] = p.w;
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const uint4 p = *reinterpret_cast<const uint4 *>(src + 8 * k);
+      t[8 * k] = p.x & 0xFFFFu; t[8 * k + 1] = p.x >> 16; t[8 * k + 2] = p.y & 0xFFFFu; t[8 * k + 3] = p.y >> 16;
+      t[8 * k + 4] = p.z & 0xFFFFu; t[8 * k + 5] = p.z >> 16; t[8 * k + 6] = p.w & 0xFFFFu; t[8 * k + 7] = p.w >> 16;
+    }
+  }
+}
+
+// the first c of 16 ids as bytes (the rest zeros); returns the OR of those c ids through *wide
+__device__ __forceinline__ uint4 bytes_of_ids16(uint32_t (&t)[16], int c, uint32_t *wide) {
+  uint32_t w = 0;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) { t[k] = k < c ? t[k] : 0u; w |= t[k]; }
+  *wide |= w;
+  auto b4 = [&t](int k) { return (t[k] & 255u) | ((t[k + 1] & 255u) << 8) | ((t[k + 2] & 255u) << 16) | (t[k + 3] << 24); };
+  return make_uint4(b4(0), b4(4), b4(8), b4(12));
+}
+
+template <typename S>
+__device__ __forceinline__ uint32_t copy_row_pieces8(const S *__restrict__ row, uint8_t *__restrict__ dst, int n, int sub, int tpr) {
+  const bool vec = ((reinterpret_cast<uintptr_t>(row) & 15u) == 0) && ((reinterpret_cast<uintptr_t>(dst) & 15u) == 0);
+  uint32_t wide = 0;
+  for (int i = sub * 16; i < n; i += tpr * 16) {
+    if (vec && i + 16 <= n) {
+      uint32_t t[16];
+      load_ids16<S>(row + i, t);
+      *reinterpret_cast<uint4 *>(dst + i) = bytes_of_ids16(t, 16, &wide);
+    } else {
+      for (int k = i; k < n && k < i + 16; ++k) {
+        const S t = row[k];
+        wide |= (uint32_t)t;
+        dst[k] = (uint8_t)t;
+      }
+    }
+  }
+  return wide;
+}
+
+// S = source id type (int32_t slab, or uint16_t: a GTOK_SENT_U16 slab), E = packed id type (uint8_t, uint16_t, int32_t or
+// int64_t).  A thread owns pieces of 8 consecutive ids of one row (16 at one byte per id: above): 16-byte loads and stores;
+// 1 << tpr_shift threads share a row, 256 >> tpr_shift rows a workgroup.
 template <typename S, typename E>
 __device__ __forceinline__ uint32_t copy_row_pieces(const S *__restrict__ row, E *__restrict__ dst, int n, int sub, int tpr) {
+  if constexpr (sizeof(E) == 1) return copy_row_pieces8<S>(row, reinterpret_cast<uint8_t *>(dst), n, sub, tpr);
   const bool vec = ((reinterpret_cast<uintptr_t>(row) & 15u) == 0) && ((reinterpret_cast<uintptr_t>(dst) & 15u) == 0);
   uint32_t wide = 0;
   for (int i = sub * 8; i < n; i += tpr * 8) {
@@ -193,7 +244,7 @@ __global__ void __launch_bounds__(256) pack_rows_kernel(const RowsArgs a) {
     return;
   }
   const uint32_t wide = copy_row_pieces<S, E>(row, reinterpret_cast<E *>(a.packed) + start, n, sub, tpr);
-  if (sizeof(E) == 2 && sizeof(S) == 4 && (wide & 0xFFFF0000u)) atomicOr(a.status, 1);     // an id that does not fit 16 bits
+  if (sizeof(E) == 1 ? (wide & ~0xFFu) != 0u : (sizeof(E) == 2 && sizeof(S) == 4 && (wide & 0xFFFF0000u))) atomicOr(a.status, 1);     // an id that does not fit 8 / 16 bits
 }
 
 // gtok_row_offsets + gtok_pack_rows(_u16) in ONE launch (gtok_pack_rows_scan): a workgroup takes a tile of 256 rows, sums
@@ -206,7 +257,7 @@ struct PackScanArgs {
   const void *ids; const int32_t *len; int64_t *row_ptr; void *packed; int32_t *status; int *ticket;
   int64_t rows, capacity;
   int ld, align_mask, tpr_shift, tiles, chunk;      // chunk: consecutive tiles per workgroup (one ticket each)
-  int fast;       // 8-id alignment, every slab row and the packed buffer on 16-byte boundaries: the flat piece loop
+  int fast;       // 8-id alignment (16 at one byte per id), every slab row and the packed buffer on 16-byte boundaries: the flat piece loop
 };
 
 __global__ void __launch_bounds__(256) pack_scan_init_kernel(int64_t *__restrict__ row_ptr, int64_t rows, int tiles, int tile_rows, int32_t *__restrict__ status) {
@@ -225,6 +276,7 @@ constexpr int kPackChunkMax = 8;
 template <typename S, typename E, int TILE>
 __global__ void __launch_bounds__(256) pack_scan_kernel(const PackScanArgs a) {
   constexpr int kPackTile = TILE, kScanWaves = TILE / kWave;
+  constexpr int PI = sizeof(E) == 1 ? 16 : 8, PSH = sizeof(E) == 1 ? 4 : 3;      // ids per 16-byte piece of the packed buffer
   __shared__ int s_tile;
   __shared__ int64_t s_wsum[4], s_base, s_start[kPackTile], s_tsum[kPackChunkMax];
   __shared__ int s_n[kPackTile], s_p[kPackTile], s_len[kPackChunkMax][kPackTile], s_part[kPackChunkMax][4];
@@ -297,18 +349,18 @@ __global__ void __launch_bounds__(256) pack_scan_kernel(const PackScanArgs a) {
   bool over = false;
   if (a.fast) {
     // 8-id pieces, flat over the tile: with 8-id alignment the tile's packed region is ONE run of whole 16-byte (E = 2 bytes)
-    // pieces, piece j of the tile landing at tile_start + 8 j.  A thread takes pieces tid, tid + 256, ... - kPackU of them per
+    // pieces, piece j of the tile landing at tile_start + 8 j (E = 1 byte: 16-id alignment, pieces of PI = 16 ids, at + 16 j).  A thread takes pieces tid, tid + 256, ... - kPackU of them per
     // pass, their loads in flight together (a row-per-thread-group loop had one load in flight per thread: 61 us for ZINC-full's
     // 44 MB in + 44 MB out, slower than the four launches it replaced) - and finds a piece's row by bisection over the rows'
     // piece offsets in LDS.  Tail pieces are loaded whole (a slab row is a multiple of 8 ids wide) and masked to zeros.
     const int64_t tbase = tbase_tile;
-    if (tid < kPackTile) s_p[tid] = (int)((start - tbase) >> 3);
+    if (tid < kPackTile) s_p[tid] = (int)((start - tbase) >> PSH);
     __syncthreads();
-    const int total_p = (int)(tile_sum >> 3);
+    const int total_p = (int)(tile_sum >> PSH);
     const int64_t row0 = (int64_t)tile * kPackTile;
     const int nrows = (int)min((int64_t)kPackTile, a.rows - row0);
     for (int j0 = tid; j0 < total_p; j0 += 256 * kPackU) {
-      uint4 lo[kPackU], hi[kPackU];
+      uint4 lo[kPackU], hi[kPackU], l2[kPackU], l3[kPackU];      // (l2 / l3: the second half of a 16-id piece of an int32 slab)
       int cnt[kPackU];
 #pragma unroll
       for (int u = 0; u < kPackU; ++u) {
@@ -321,10 +373,12 @@ __global__ void __launch_bounds__(256) pack_scan_kernel(const PackScanArgs a) {
           const int64_t st = s_start[b0];
           if (st + s_n[b0] > a.capacity) { over = true; }
           else {
-            cnt[u] = min(8, s_n[b0] - 8 * q);
-            const S *src = reinterpret_cast<const S *>(a.ids) + (row0 + b0) * (int64_t)a.ld + 8 * q;
+            cnt[u] = min(PI, s_n[b0] - PI * q);
+            const S *src = reinterpret_cast<const S *>(a.ids) + (row0 + b0) * (int64_t)a.ld + PI * q;
             lo[u] = *reinterpret_cast<const uint4 *>(src);
             if (sizeof(S) == 4) hi[u] = *reinterpret_cast<const uint4 *>(src + 4);
+            if (sizeof(E) == 1 && sizeof(S) == 2) hi[u] = *reinterpret_cast<const uint4 *>(src + 8);
+            if (sizeof(E) == 1 && sizeof(S) == 4) { l2[u] = *reinterpret_cast<const uint4 *>(src + 8); l3[u] = *reinterpret_cast<const uint4 *>(src + 12); }
           }
         }
       }
@@ -332,6 +386,18 @@ __global__ void __launch_bounds__(256) pack_scan_kernel(const PackScanArgs a) {
       for (int u = 0; u < kPackU; ++u) {
         if (cnt[u] <= 0) continue;
         const int c = cnt[u];
+        if constexpr (sizeof(E) == 1) {
+          uint32_t b[16];
+          auto two = [&b](int k, uint32_t w) { b[k] = w & 0xFFFFu; b[k + 1] = w >> 16; };
+          if (sizeof(S) == 4) {
+            b[0] = lo[u].x; b[1] = lo[u].y; b[2] = lo[u].z; b[3] = lo[u].w; b[4] = hi[u].x; b[5] = hi[u].y; b[6] = hi[u].z; b[7] = hi[u].w;
+            b[8] = l2[u].x; b[9] = l2[u].y; b[10] = l2[u].z; b[11] = l2[u].w; b[12] = l3[u].x; b[13] = l3[u].y; b[14] = l3[u].z; b[15] = l3[u].w;
+          } else {
+            two(0, lo[u].x); two(2, lo[u].y); two(4, lo[u].z); two(6, lo[u].w); two(8, hi[u].x); two(10, hi[u].y); two(12, hi[u].z); two(14, hi[u].w);
+          }
+          *reinterpret_cast<uint4 *>(reinterpret_cast<uint8_t *>(a.packed) + tbase + 16 * (int64_t)(j0 + u * 256)) = bytes_of_ids16(b, c, &wide);
+          continue;
+        }
         uint32_t t[8];
         if (sizeof(S) == 4) {
           t[0] = lo[u].x; t[1] = lo[u].y; t[2] = lo[u].z; t[3] = lo[u].w; t[4] = hi[u].x; t[5] = hi[u].y; t[6] = hi[u].z; t[7] = hi[u].w;
@@ -372,7 +438,7 @@ __global__ void __launch_bounds__(256) pack_scan_kernel(const PackScanArgs a) {
     }
     if (over && sub == 0) atomicOr(a.status, 2);
   }
-  if (sizeof(E) == 2 && sizeof(S) == 4 && (wide & 0xFFFF0000u)) atomicOr(a.status, 1);
+  if (sizeof(E) == 1 ? (wide & ~0xFFu) != 0u : (sizeof(E) == 2 && sizeof(S) == 4 && (wide & 0xFFFF0000u))) atomicOr(a.status, 1);
   __syncthreads();      // the tile's LDS tables are free again
   }
 }
@@ -411,7 +477,11 @@ __global__ void __launch_bounds__(256) unpack_rows_kernel(const RowsArgs a) {
 #pragma unroll
       for (int k = 0; k < 8; ++k) v[k] = pad;
       if (i + 8 <= n) {
-        if (sizeof(E) == 2) {
+        if (sizeof(E) == 1) {                              // eight ids = one 8-byte load (src is 16-byte aligned, i a multiple of 8)
+          const uint2 p = *reinterpret_cast<const uint2 *>(src + i);
+#pragma unroll
+          for (int k = 0; k < 4; ++k) { v[k] = (int)((p.x >> (8 * k)) & 255u); v[4 + k] = (int)((p.y >> (8 * k)) & 255u); }
+        } else if (sizeof(E) == 2) {
           const uint4 p = *reinterpret_cast<const uint4 *>(src + i);
           v[0] = (int)(p.x & 0xFFFFu); v[1] = (int)(p.x >> 16); v[2] = (int)(p.y & 0xFFFFu); v[3] = (int)(p.y >> 16);
           v[4] = (int)(p.z & 0xFFFFu); v[5] = (int)(p.z >> 16); v[6] = (int)(p.w & 0xFFFFu); v[7] = (int)(p.w >> 16);
@@ -711,7 +781,7 @@ static int rows_launch(bool pack, const void *ids, int src_bytes, void *out_ids,
                        void *packed, int64_t capacity, int32_t pad_id, int32_t *status, void *stream, int at = 0) {
   DeviceScope device_scope((hipStream_t)stream);
   if (!device_scope.ok()) return GTOK_E_NO_DEVICE;
-  const bool eb_ok = elem_bytes == 2 || elem_bytes == 4 || (pack && src_bytes == 2 && elem_bytes == 8);
+  const bool eb_ok = elem_bytes == 1 || elem_bytes == 2 || elem_bytes == 4 || (pack && src_bytes == 2 && elem_bytes == 8);
   if (num_rows < 0 || ld <= 0 || !eb_ok || segment_stride < 0 || segment_rows < 0) return GTOK_E_INVAL;
   if (num_rows == 0) return GTOK_OK;
   if (!len || !packed || (pack ? (!ids || !row_ptr) : !out_ids) || (pack && !status) || capacity < 0) return GTOK_E_INVAL;
@@ -733,11 +803,13 @@ static int rows_launch(bool pack, const void *ids, int src_bytes, void *out_ids,
   if (nb > 0x7FFFFFFF) return GTOK_E_TOO_LARGE;
   hipStream_t s = (hipStream_t)stream;
   if (pack && src_bytes == 2) {
-    if (elem_bytes == 2) hipLaunchKernelGGL((pack_rows_kernel<uint16_t, uint16_t>), dim3((unsigned)nb), dim3(256), 0, s, a);
+    if (elem_bytes == 1) hipLaunchKernelGGL((pack_rows_kernel<uint16_t, uint8_t>), dim3((unsigned)nb), dim3(256), 0, s, a);
+    else if (elem_bytes == 2) hipLaunchKernelGGL((pack_rows_kernel<uint16_t, uint16_t>), dim3((unsigned)nb), dim3(256), 0, s, a);
     else if (elem_bytes == 4) hipLaunchKernelGGL((pack_rows_kernel<uint16_t, int32_t>), dim3((unsigned)nb), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((pack_rows_kernel<uint16_t, int64_t>), dim3((unsigned)nb), dim3(256), 0, s, a);
   } else if (pack) {
-    if (elem_bytes == 2) hipLaunchKernelGGL((pack_rows_kernel<int32_t, uint16_t>), dim3((unsigned)nb), dim3(256), 0, s, a);
+    if (elem_bytes == 1) hipLaunchKernelGGL((pack_rows_kernel<int32_t, uint8_t>), dim3((unsigned)nb), dim3(256), 0, s, a);
+    else if (elem_bytes == 2) hipLaunchKernelGGL((pack_rows_kernel<int32_t, uint16_t>), dim3((unsigned)nb), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((pack_rows_kernel<int32_t, int32_t>), dim3((unsigned)nb), dim3(256), 0, s, a);
   } else {
     int per_cu = kUnpackWgPerCu;
@@ -745,10 +817,12 @@ static int rows_launch(bool pack, const void *ids, int src_bytes, void *out_ids,
     const int64_t cap_wg = per_cu > 0 ? (int64_t)device_cu_count(device_scope.dev) * per_cu : nb;
     const unsigned nu = (unsigned)(nb < cap_wg ? nb : cap_wg);
     if (out_bytes == 2) {
-      if (elem_bytes == 2) hipLaunchKernelGGL((unpack_rows_kernel<uint16_t, uint16_t>), dim3(nu), dim3(256), 0, s, a);
+      if (elem_bytes == 1) hipLaunchKernelGGL((unpack_rows_kernel<uint8_t, uint16_t>), dim3(nu), dim3(256), 0, s, a);
+      else if (elem_bytes == 2) hipLaunchKernelGGL((unpack_rows_kernel<uint16_t, uint16_t>), dim3(nu), dim3(256), 0, s, a);
       else hipLaunchKernelGGL((unpack_rows_kernel<int32_t, uint16_t>), dim3(nu), dim3(256), 0, s, a);
     } else {
-      if (elem_bytes == 2) hipLaunchKernelGGL((unpack_rows_kernel<uint16_t, int32_t>), dim3(nu), dim3(256), 0, s, a);
+      if (elem_bytes == 1) hipLaunchKernelGGL((unpack_rows_kernel<uint8_t, int32_t>), dim3(nu), dim3(256), 0, s, a);
+      else if (elem_bytes == 2) hipLaunchKernelGGL((unpack_rows_kernel<uint16_t, int32_t>), dim3(nu), dim3(256), 0, s, a);
       else hipLaunchKernelGGL((unpack_rows_kernel<int32_t, int32_t>), dim3(nu), dim3(256), 0, s, a);
     }
   }
@@ -759,7 +833,7 @@ extern "C" int gtok_pack_rows_scan(const void *ids, int32_t src_bytes, int32_t l
                                    int32_t elem_bytes, void *packed, int64_t capacity, int64_t *row_ptr, int32_t *status, void *stream) {
   DeviceScope device_scope((hipStream_t)stream);
   if (!device_scope.ok()) return GTOK_E_NO_DEVICE;
-  const bool eb_ok = elem_bytes == 2 || elem_bytes == 4 || (src_bytes == 2 && elem_bytes == 8);
+  const bool eb_ok = elem_bytes == 1 || elem_bytes == 2 || elem_bytes == 4 || (src_bytes == 2 && elem_bytes == 8);
   if (num_rows < 0 || ld <= 0 || (src_bytes != 2 && src_bytes != 4) || !eb_ok || align < 1 || (align & (align - 1)) || capacity < 0 || !row_ptr)
     return GTOK_E_INVAL;
   hipStream_t s = (hipStream_t)stream;
@@ -781,7 +855,8 @@ extern "C" int gtok_pack_rows_scan(const void *ids, int32_t src_bytes, int32_t l
   if (sh > 0) --sh;
   a.tpr_shift = sh;
   // (the fast path stores a row's last piece whole: only a capacity of whole pieces keeps that store inside the buffer)
-  a.fast = align == 8 && ((int64_t)ld * src_bytes) % 16 == 0 && ld % 8 == 0 && capacity % 8 == 0 && (reinterpret_cast<uintptr_t>(ids) & 15u) == 0 &&
+  const int piece = elem_bytes == 1 ? 16 : 8;        // ids per 16-byte piece of the fast path (8 ids of 4 or 8 bytes: two / four stores)
+  a.fast = align == piece && ((int64_t)ld * src_bytes) % 16 == 0 && ld % piece == 0 && capacity % piece == 0 && (reinterpret_cast<uintptr_t>(ids) & 15u) == 0 &&
            (reinterpret_cast<uintptr_t>(packed) & 15u) == 0;
   a.chunk = (int)((tiles + 8ll * ncu - 1) / (8ll * ncu));
   if (a.chunk < 1) a.chunk = 1;
@@ -795,11 +870,13 @@ extern "C" int gtok_pack_rows_scan(const void *ids, int32_t src_bytes, int32_t l
     else hipLaunchKernelGGL((pack_scan_kernel<S_, E_, 64>), grid, block, 0, s, a);                          \
   } while (0)
   if (src_bytes == 2) {
-    if (elem_bytes == 2) GTOK_PACK_SCAN(uint16_t, uint16_t);
+    if (elem_bytes == 1) GTOK_PACK_SCAN(uint16_t, uint8_t);
+    else if (elem_bytes == 2) GTOK_PACK_SCAN(uint16_t, uint16_t);
     else if (elem_bytes == 4) GTOK_PACK_SCAN(uint16_t, int32_t);
     else GTOK_PACK_SCAN(uint16_t, int64_t);
   } else {
-    if (elem_bytes == 2) GTOK_PACK_SCAN(int32_t, uint16_t);
+    if (elem_bytes == 1) GTOK_PACK_SCAN(int32_t, uint8_t);
+    else if (elem_bytes == 2) GTOK_PACK_SCAN(int32_t, uint16_t);
     else GTOK_PACK_SCAN(int32_t, int32_t);
   }
 #undef GTOK_PACK_SCAN
@@ -852,12 +929,15 @@ extern "C" int gtok_collate_packed(const void *packed, int32_t elem_bytes, const
                                    uint8_t *out_attn, int32_t out_ld, void *stream) {
   DeviceScope device_scope((hipStream_t)stream);
   if (!device_scope.ok()) return GTOK_E_NO_DEVICE;
-  if (!packed || !len || !index || ld <= 0 || batch < 0 || out_ld < 0 || (elem_bytes != 2 && elem_bytes != 4))
+  if (!packed || !len || !index || ld <= 0 || batch < 0 || out_ld < 0 || (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4))
     return GTOK_E_INVAL;      // (row_ptr == NULL: the strided form)
   if (batch == 0 || out_ld == 0) return GTOK_OK;
   if (!out_x || !out_attn) return GTOK_E_INVAL;
   hipStream_t s = (hipStream_t)stream;
-  if (elem_bytes == 2)
+  if (elem_bytes == 1)
+    hipLaunchKernelGGL(collate_packed_kernel<uint8_t>, dim3((batch + 3) / 4), dim3(256), 0, s, packed, row_ptr, len, ld, index,
+                       batch, pad_id, out_x, out_attn, out_ld);
+  else if (elem_bytes == 2)
     hipLaunchKernelGGL(collate_packed_kernel<uint16_t>, dim3((batch + 3) / 4), dim3(256), 0, s, packed, row_ptr, len, ld, index,
                        batch, pad_id, out_x, out_attn, out_ld);
   else
@@ -871,7 +951,7 @@ extern "C" int gtok_collate_batch(const void *packed, int32_t elem_bytes, const 
                                   int32_t out_ld, const void *y, int32_t y_bytes, void *out_y, void *stream) {
   DeviceScope device_scope((hipStream_t)stream);
   if (!device_scope.ok()) return GTOK_E_NO_DEVICE;
-  if (batch < 0 || ld <= 0 || out_ld < 0 || num_rows < 0 || (elem_bytes != 2 && elem_bytes != 4) || (y && (y_bytes < 1 || y_bytes > 8 || !out_y)))
+  if (batch < 0 || ld <= 0 || out_ld < 0 || num_rows < 0 || (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4) || (y && (y_bytes < 1 || y_bytes > 8 || !out_y)))
     return GTOK_E_INVAL;
   if (batch == 0) return GTOK_OK;
   if (!packed || !len || !host_index || (out_ld > 0 && (!out_x || !out_attn))) return GTOK_E_INVAL;
@@ -886,7 +966,8 @@ extern "C" int gtok_collate_batch(const void *packed, int32_t elem_bytes, const 
     const int cnt = batch - first < kBatchArgIdx ? batch - first : kBatchArgIdx;
     a.batch = cnt; a.first = first;
     for (int i = 0; i < cnt; ++i) a.index[i] = (int32_t)host_index[first + i];
-    if (elem_bytes == 2) hipLaunchKernelGGL(collate_batch_kernel<uint16_t>, dim3((cnt + 3) / 4), dim3(256), 0, s, a);
+    if (elem_bytes == 1) hipLaunchKernelGGL(collate_batch_kernel<uint8_t>, dim3((cnt + 3) / 4), dim3(256), 0, s, a);
+    else if (elem_bytes == 2) hipLaunchKernelGGL(collate_batch_kernel<uint16_t>, dim3((cnt + 3) / 4), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(collate_batch_kernel<int32_t>, dim3((cnt + 3) / 4), dim3(256), 0, s, a);
   }
   return hipGetLastError() == hipSuccess ? GTOK_OK : GTOK_E_LAUNCH;
@@ -911,13 +992,16 @@ extern "C" int gtok_collate_epoch(const void *packed, int32_t elem_bytes, const 
                                   const int64_t *batch_off, int64_t *out_x, uint8_t *out_attn, int64_t arena_elems, void *stream) {
   DeviceScope device_scope((hipStream_t)stream);
   if (!device_scope.ok()) return GTOK_E_NO_DEVICE;
-  if (n < 0 || ld <= 0 || batch_size <= 0 || arena_elems < 0 || (elem_bytes != 2 && elem_bytes != 4)) return GTOK_E_INVAL;
+  if (n < 0 || ld <= 0 || batch_size <= 0 || arena_elems < 0 || (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4)) return GTOK_E_INVAL;
   if (n == 0) return GTOK_OK;
   if (!packed || !len || !order || !batch_lmax || !batch_off || !out_x || !out_attn) return GTOK_E_INVAL;
   if ((n + 3) / 4 > 0x7FFFFFFF) return GTOK_E_TOO_LARGE;
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)((n + 3) / 4)), block(256);
-  if (elem_bytes == 2)
+  if (elem_bytes == 1)
+    hipLaunchKernelGGL(collate_epoch_kernel<uint8_t>, grid, block, 0, s, packed, row_ptr, len, ld, order, n, batch_size, pad_id, batch_lmax, batch_off,
+                       out_x, out_attn, arena_elems);
+  else if (elem_bytes == 2)
     hipLaunchKernelGGL(collate_epoch_kernel<uint16_t>, grid, block, 0, s, packed, row_ptr, len, ld, order, n, batch_size, pad_id, batch_lmax, batch_off,
                        out_x, out_attn, arena_elems);
   else

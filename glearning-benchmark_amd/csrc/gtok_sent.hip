@@ -89,8 +89,10 @@ static int sent_impl(const gtok_csr *g, const gtok_sent_params *p, int32_t *out_
   if (!out_ids || !out_len) return GTOK_E_INVAL;
   if (!g->node_ptr || !g->edge_ptr || !g->rowptr || (g->max_edges > 0 && !g->col)) return GTOK_E_INVAL;
   if (p->max_len < 0 || p->max_num_nodes < 0 || p->epoch_count < 0 || p->reserved != 0) return GTOK_E_INVAL;
-  if (p->flags & ~(GTOK_SENT_NO_PAD | GTOK_SENT_U16 | (pd ? GTOK_SENT_PACK_ONLY : 0))) return GTOK_E_INVAL;
+  if (p->flags & ~(GTOK_SENT_NO_PAD | GTOK_SENT_U16 | (pd ? GTOK_SENT_PACK_ONLY | GTOK_SENT_PACK_U8 : 0))) return GTOK_E_INVAL;
   const bool u16 = (p->flags & GTOK_SENT_U16) != 0;
+  const bool pk8 = (p->flags & GTOK_SENT_PACK_U8) != 0;      // one byte per id in the packed buffer; the slab / staging rows stay 16-bit
+  if (pk8 && !u16) return GTOK_E_INVAL;
   if (u16 && (p->pad_id < 0 || p->pad_id > 65535)) return GTOK_E_INVAL;   // (the id space itself is checked below: tokens are 16 bits inside the kernels anyway)
   const int K = sent_epochs(p);
   if ((int64_t)g->num_graphs * K > 0x7FFFFFFF / 2) return GTOK_E_TOO_LARGE;   // rows of the [K, G, ld] slab are counted in 32 bits
@@ -112,7 +114,7 @@ static int sent_impl(const gtok_csr *g, const gtok_sent_params *p, int32_t *out_
     if (which != 0) return GTOK_E_UNSUPPORTED;
     if (!pd->packed || !pd->row_start || !pd->state || pd->capacity < 0) return GTOK_E_INVAL;
     if (ld > (u16 ? 2040 : 1020)) return GTOK_E_TOO_LARGE;    // (a row's 16-byte pieces are counted in 8 bits)
-    if (ld % (u16 ? 8 : 4) != 0 || (reinterpret_cast<uintptr_t>(out_ids) & 15u) || (reinterpret_cast<uintptr_t>(pd->packed) & 15u)) return GTOK_E_INVAL;
+    if (ld % (pk8 ? 16 : u16 ? 8 : 4) != 0 || (reinterpret_cast<uintptr_t>(out_ids) & 15u) || (reinterpret_cast<uintptr_t>(pd->packed) & 15u)) return GTOK_E_INVAL;
   }
   // padding with non-temporal stores once the slab outgrows the memory-side cache (256 MB on MI355X): gtok_sent_lane.hpp
   int pad_nt = (int64_t)g->num_graphs * K * ld * (u16 ? 2 : 4) > ((int64_t)256 << 20);
@@ -199,6 +201,11 @@ static int sent_impl(const gtok_csr *g, const gtok_sent_params *p, int32_t *out_
       kern = !p->labeled ? GTOK_LANE_KP(false, false) : p->remap_zinc ? GTOK_LANE_KP(true, true) : GTOK_LANE_KP(true, false);
 #undef GTOK_LANE_KP
 #undef GTOK_LANE_KP2
+      if (pk8) {
+#define GTOK_LANE_KP8(LAB, REMAP) (p3 ? (KF)sent_lane_kernel<LAB, 4, REMAP, true, true, true, true> : (KF)sent_lane_kernel<LAB, 6, REMAP, true, true, true, true>)
+        kern = !p->labeled ? GTOK_LANE_KP8(false, false) : p->remap_zinc ? GTOK_LANE_KP8(true, true) : GTOK_LANE_KP8(true, false);
+#undef GTOK_LANE_KP8
+      }
     }
     const int dev = device_scope.dev, ncu = device_cu_count(dev);
     int occ = -1;                                 // occupancy of one-wave workgroups: only the fallback launch below asks
@@ -218,7 +225,7 @@ static int sent_impl(const gtok_csr *g, const gtok_sent_params *p, int32_t *out_
       int m = GTOK_PACK_REGIONS;
       while (m > 1 && vunits < 64 * m) m >>= 1;
       a.pack_regions = m;
-      a.pack_region_cap = (pd->capacity / m) & ~(int64_t)7;
+      a.pack_region_cap = (pd->capacity / m) & ~(int64_t)(pk8 ? 15 : 7);
     }
     // order of the pairs: unit-major (the K walks of a unit side by side: the deal stays sorted by walk length) for splits that
     // need several epochs to fill the chip; epoch-major (epoch 0 of every unit, then epoch 1, ...) when one epoch fills half of

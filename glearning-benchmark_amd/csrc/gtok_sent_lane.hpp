@@ -189,7 +189,7 @@ struct SentLaneArgs {
   void *pack_out;
   int64_t *pack_start;              // [K * G] first id of row (epoch, graph) in pack_out; -1: did not fit
   unsigned long long *pack_state;   // GTOK_PACK_STATE_WORDS words: [0] status bits, [FILL + STRIDE * r] ids used in region r
-  int64_t pack_region_cap;          // ids per region (a multiple of 8)
+  int64_t pack_region_cap;          // ids per region (a multiple of 8; of 16 with GTOK_SENT_PACK_U8)
   int pack_regions;                 // a power of two <= GTOK_PACK_REGIONS
   int pack_scratch;                 // GTOK_SENT_PACK_ONLY: `out` is staging space, 64 rows per resident wave
 };
@@ -199,7 +199,9 @@ struct SentLaneArgs {
 // U16: the GTOK_SENT_U16 slab - rows of 16-bit ids, the token windows stored as they stand
 // PACK: gtok_sent_packed - a finished unit's rows are also appended to the packed buffer (an instantiation of its own: the plain
 // kernel's register allocation is not to be touched)
-template <bool LAB, int P, bool REMAP, bool PK, bool U16, bool PACK = false>
+// PK8: GTOK_SENT_PACK_U8 (with U16 and PACK only) - the packed buffer holds ONE byte per id: the copy at a unit's end narrows two
+// 16-byte pieces of a staged row into one.  Every line of it sits behind `if constexpr`: the other instantiations are untouched
+template <bool LAB, int P, bool REMAP, bool PK, bool U16, bool PACK = false, bool PK8 = false>
 __global__ void __launch_bounds__(1024) sent_lane_kernel(const SentLaneArgs a) {
   using out_t = typename std::conditional<U16, uint16_t, int32_t>::type;
   constexpr int EV = U16 ? 8 : 4;            // ids per 16-byte store
@@ -836,14 +838,17 @@ __global__ void __launch_bounds__(1024) sent_lane_kernel(const SentLaneArgs a) {
       const uint64_t tp0 = __builtin_amdgcn_s_memtime();
       uint64_t tp1 = tp0;
 #endif
+      constexpr int PEV = PK8 ? 16 : EV;           // ids per 16-byte piece of the packed buffer
       const int nid = valid ? min(tot, ld) : 0;
-      const int np = (nid + EV - 1) / EV;
+      const int np = (nid + PEV - 1) / PEV;
       const int inc = wave_incl_scan_dpp(np);
       const int total = __builtin_amdgcn_readlane(inc, kWave - 1);
       const int region = vu & (a.pack_regions - 1);
       const int cnt = h.gl - h.g0;
       const int q = lane & 15, grp = lane >> 4;
-      const int my_row = valid ? (int)srow : -1, my_offnp = ((inc - np) << 8) | np;   // (np <= 255: the launcher checks ld)
+      // (np <= 255: the launcher checks ld.  PK8: the row's length in ids travels instead of its piece count - ld <= 2040 fits 12 bits,
+      // the offset stays below 64 * 128 pieces - because the narrowing has to know which ids of a row's last piece are the row's)
+      const int my_row = valid ? (int)srow : -1, my_offnp = PK8 ? ((inc - np) << 12) | nid : ((inc - np) << 8) | np;
       const int my_row0 = __builtin_amdgcn_readfirstlane((int)srow);               // (a row of this unit: lane 0 is always valid)
       // The rows read below were written by this wave (other lanes of it).  A CU's stores and loads go through the one vector cache,
       // which must keep a work-item's own store -> load coherent (a write hit updates or drops the line) and does so per address,
@@ -854,7 +859,10 @@ __global__ void __launch_bounds__(1024) sent_lane_kernel(const SentLaneArgs a) {
       // A sweep = 16-byte piece 16 sweep + q of every row, in two batches of eight passes of four rows (what the register file has
       // room for at a unit's end; variants measured slower or equal: the copy behind the next unit's staging loads - its state
       // lives across the walk and spills -, double-buffered batches of four, passes 8-15 landed in LDS by global_load_lds)
-      constexpr int KF = 8;
+      // (PK8: a pass fetches two pieces per row, so four rows per lane and batch keep the same 32 registers of loads in flight; eight
+      // were tried: 64 registers of loads do not fit beside the copy's own state - 200-248 bytes of scratch per lane)
+      constexpr int KF = PK8 ? 4 : 8;
+      [[maybe_unused]] uint32_t wide8 = 0;         // PK8: the high bytes of every id this lane narrowed
       bool fits = true, placed = false;
       gtok_v4i *dstbase = nullptr;
       for (int sweep = 0;; ++sweep) {
@@ -863,12 +871,24 @@ __global__ void __launch_bounds__(1024) sent_lane_kernel(const SentLaneArgs a) {
         for (int b0 = 0; b0 < 16; b0 += KF) {
           if (b0 * 4 >= cnt) break;
           gtok_v4i v[KF];
+          [[maybe_unused]] gtok_v4i v2[PK8 ? KF : 1];    // PK8: the second 16-byte piece of the pair (ids 16 t + 8 .. 16 t + 15)
+          [[maybe_unused]] int rem[PK8 ? KF : 1];        // PK8: ids of the row from 16 t on
           int doff[KF];
 #pragma unroll
           for (int k = 0; k < KF; ++k) {
             const int rn = ((b0 + k) * 4 + grp) << 2;
             const int r_idx = __builtin_amdgcn_ds_bpermute(rn, my_row);
             const int r_on = __builtin_amdgcn_ds_bpermute(rn, my_offnp);
+            if constexpr (PK8) {
+              rem[k] = r_idx >= 0 ? (r_on & 4095) - 16 * t : 0;
+              const bool on8 = rem[k] > 0;
+              doff[k] = on8 ? (r_on >> 12) + t : -1;
+              // (ld % 16 == 0: a staged row is whole pairs of pieces, so the second piece of a row's last pair is inside the row)
+              const gtok_v4i *src8 = reinterpret_cast<const gtok_v4i *>(out_base + (int64_t)(on8 ? r_idx : my_row0) * ld) + (on8 ? 2 * t : 0);
+              v[k] = src8[0];
+              v2[k] = src8[1];
+              continue;
+            }
             const bool on = r_idx >= 0 && t < (r_on & 255);
             doff[k] = on ? (r_on >> 8) + t : -1;
             // (an address is always formed - a row of this unit for the lanes that have nothing to fetch - so that the loads leave
@@ -885,17 +905,18 @@ __global__ void __launch_bounds__(1024) sent_lane_kernel(const SentLaneArgs a) {
             unsigned long long base = 0;
 #ifndef GTOK_PACK_ABLATE_ATOMIC
             if (lane == 0)
-              base = __hip_atomic_fetch_add(a.pack_state + GTOK_PACK_STATE_FILL + GTOK_PACK_STATE_STRIDE * region, (unsigned long long)total * EV,
+              base = __hip_atomic_fetch_add(a.pack_state + GTOK_PACK_STATE_FILL + GTOK_PACK_STATE_STRIDE * region, (unsigned long long)total * PEV,
                                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             base = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32)) << 32) |
                    (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
 #else
             base = (unsigned long long)(vu / a.pack_regions) * 64 * 96;
 #endif
-            fits = base + (unsigned long long)total * EV <= (unsigned long long)a.pack_region_cap;
+            fits = base + (unsigned long long)total * PEV <= (unsigned long long)a.pack_region_cap;
             const int64_t rstart = (int64_t)region * a.pack_region_cap + (int64_t)base;
-            dstbase = reinterpret_cast<gtok_v4i *>(reinterpret_cast<out_t *>(a.pack_out) + rstart);
-            if (valid) a.pack_start[orow_idx] = fits ? rstart + (int64_t)(inc - np) * EV : (int64_t)-1;
+            if constexpr (PK8) dstbase = reinterpret_cast<gtok_v4i *>(reinterpret_cast<uint8_t *>(a.pack_out) + rstart);
+            else dstbase = reinterpret_cast<gtok_v4i *>(reinterpret_cast<out_t *>(a.pack_out) + rstart);
+            if (valid) a.pack_start[orow_idx] = fits ? rstart + (int64_t)(inc - np) * PEV : (int64_t)-1;
             if (!fits && lane == 0 && total > 0) atomicOr(a.pack_state, 2ull);
 #ifdef GTOK_PHASE_TIMING
             tp1 = __builtin_amdgcn_s_memtime();
@@ -904,12 +925,34 @@ __global__ void __launch_bounds__(1024) sent_lane_kernel(const SentLaneArgs a) {
 #ifdef GTOK_PACK_ABLATE_COPY
           if (total == 0x7654321)
 #endif
+          if constexpr (PK8) {
+            // two pieces of 16-bit ids -> one of bytes: v_perm_b32 gathers the low bytes (what is stored) and the high bytes (what
+            // must be zero) of a register pair; the ids behind the row's end - pad ids, or whatever the staging row held - are
+            // masked out of both, so the packed row's alignment tail is zeros and cannot raise the flag
+#pragma unroll
+            for (int k = 0; k < KF; ++k) {
+              const uint32_t s[8] = {(uint32_t)v[k].x, (uint32_t)v[k].y, (uint32_t)v[k].z, (uint32_t)v[k].w,
+                                     (uint32_t)v2[k].x, (uint32_t)v2[k].y, (uint32_t)v2[k].z, (uint32_t)v2[k].w};
+              uint32_t lo4[4];
+#pragma unroll
+              for (int j = 0; j < 4; ++j) {
+                const int c = rem[k] - 4 * j;      // ids of the row in bytes 4 j .. 4 j + 3 of the piece
+                const uint32_t m = c >= 4 ? 0xFFFFFFFFu : (c <= 0 ? 0u : (1u << (8 * c)) - 1u);
+                lo4[j] = __builtin_amdgcn_perm(s[2 * j + 1], s[2 * j], 0x06040200u) & m;
+                wide8 |= __builtin_amdgcn_perm(s[2 * j + 1], s[2 * j], 0x07050301u) & m;
+              }
+              v[k] = gtok_v4i{(int)lo4[0], (int)lo4[1], (int)lo4[2], (int)lo4[3]};
+            }
+          }
           if (fits) {
 #pragma unroll
             for (int k = 0; k < KF; ++k) if (doff[k] >= 0) dstbase[doff[k]] = v[k];
           }
         }
         if (__ballot(np > 16 * (sweep + 1)) == 0) break;
+      }
+      if constexpr (PK8) {      // an id that does not fit 8 bits: one atomic per wave that saw one (as bit 1 above)
+        if (__ballot(wide8 != 0u) != 0 && lane == 0) atomicOr(a.pack_state, 1ull);
       }
 #ifdef GTOK_PHASE_TIMING
       pkt[0] = tp1 - tp0; pkt[1] = __builtin_amdgcn_s_memtime() - tp1;

@@ -27,6 +27,22 @@ def all_reduce_max_int(value: int, device) -> int:
     return int(t.item())
 
 
+ID_TOO_WIDE_8 = "an id does not fit 8 bits: use 16-bit packed rows"
+
+
+def _or_status(col: torch.Tensor) -> torch.Tensor:
+    """the ranks' status words ORed (bit 0: an id did not fit, bit 1: rows did not fit) -> int32 [1]"""
+    return ((col & 1).max() | (col & 2).max()).to(torch.int32).reshape(1)
+
+
+def _fail_if_too_wide(verdict: torch.Tensor, elem_bytes: int) -> None:
+    """8-bit rows: whether every id fits is a property of the data, and a buffer with an id that did not is not to be used - the
+    agreed verdict (the same tensor on every rank) is read here and every rank raises together, after the collectives"""
+    if elem_bytes == 1 and int(verdict.item()) & 1:
+        from ._lib import GtokError
+        raise GtokError("gather_tokens: " + ID_TOO_WIDE_8)
+
+
 def shard_of(batch, rank: int = None, world: int = None):
     """(this rank's block of `batch` as its own GraphBatch, lo, hi): tokenize it with graph_base=lo."""
     if world is None:
@@ -49,13 +65,15 @@ def gather_tokens(ids: torch.Tensor, ln: torch.Tensor, num_graphs: int, pad_id: 
     slab: the padded one moves half the bytes, the compact one packs the rows as they are and re-pads at 16 bits).
 
     compact=True moves the PACKED form over the links instead of the padded slab (include/gtok.h, "packed rows"): every
-    rank packs its rows back to back at `elem_bytes` (2: every SENT / IBTT id fits 16 bits; 4 otherwise) per id
+    rank packs its rows back to back at `elem_bytes` (2: every SENT / IBTT id fits 16 bits; 4 otherwise; 1: every id is below
+    256, as in remapped and un-remapped ZINC molecules - rows then start at multiples of 16 ids and capacities count bytes) per id
     (gtok_pack_rows), the packed buffers - sized to the largest rank's total, one all_reduce(MAX) of an int, or to
     `capacity` elements when the caller knows a bound (then nothing waits for the host) - and the lengths are gathered, and
     every rank re-pads locally at HBM speed (gtok_unpack_rows).  More than half of a ZINC slab is padding and ids are 32
     bits wide there: 208 MB per corpus become ~46 MB.  Same result as the padded path, bit for bit.
     Every rank's pack status travels WITH its lengths (one more int per rank in the same collective), so all ranks see the
-    same verdict: bit 0 = an id did not fit 16 bits, bit 1 = a rank's rows did not fit `capacity` (those rows come out as
+    same verdict: bit 0 = an id did not fit 16 bits (8 bits at elem_bytes=1: every rank then raises whatever the capacity's
+    origin - such a buffer is not to be used), bit 1 = a rank's rows did not fit `capacity` (those rows come out as
     all pad: gtok_unpack_rows never reads beyond a rank's segment).  Without a caller-given capacity a nonzero status
     raises - on every rank, after the collectives, so nobody is left waiting in one; with it, stats["status"] holds the
     verdict as a device tensor for the caller to read when it likes.
@@ -103,13 +121,15 @@ def gather_tokens(ids: torch.Tensor, ln: torch.Tensor, num_graphs: int, pad_id: 
     pack = rows_impl.pack_rows_u16 if ids.dtype == torch.int16 else rows_impl.pack_rows
     caller_bound = capacity is not None
     row_ptr = None
+    al = 16 if elem_bytes == 1 else 8                       # ids per 16 bytes: row starts and segments stay 16-byte aligned
+    akw = {"align": al} if elem_bytes == 1 else {}
     if not caller_bound:
-        row_ptr = rows_impl.row_offsets(ln, ld)
+        row_ptr = rows_impl.row_offsets(ln, ld, **akw)
         capacity = all_reduce_max_int(int(row_ptr[-1]), ids.device)
-    capacity = max(8, -(-int(capacity) // 8) * 8)           # keeps every rank's segment 16-byte aligned
+    capacity = max(al, -(-int(capacity) // al) * al)        # keeps every rank's segment 16-byte aligned
     # (a caller-given bound - e.g. last epoch's size plus a margin - means no size exchange, no host round trip at all, and
     # offsets + packing in ONE pass: gtok_pack_rows_scan)
-    packed, _, status = pack(ids, ln, row_ptr, elem_bytes, capacity=capacity, check_status=False)
+    packed, _, status = pack(ids, ln, row_ptr, elem_bytes, capacity=capacity, check_status=False, **akw)
     all_packed = torch.empty(world * capacity, dtype=packed.dtype, device=packed.device)
     dist.all_gather_into_tensor(all_packed.view(torch.uint8), packed[:capacity].contiguous().view(torch.uint8))
     ext = torch.cat([ln, status.to(ln.dtype).reshape(1)])   # lengths + this rank's pack status, one collective
@@ -117,13 +137,14 @@ def gather_tokens(ids: torch.Tensor, ln: torch.Tensor, num_graphs: int, pad_id: 
     dist.all_gather_into_tensor(all_ext, ext)
     all_ext = all_ext.view(world, per + 1)
     all_ln = all_ext[:, :per].reshape(-1).contiguous()
-    all_ptr = rows_impl.row_offsets(all_ln, ld)
+    all_ptr = rows_impl.row_offsets(all_ln, ld, **akw)
     ustatus = torch.zeros(1, dtype=torch.int32, device=ln.device)
     # 16-bit rows in, 16-bit slab out (as the padded exchange does): the re-padding pass writes half the bytes
     u16 = ids.dtype == torch.int16
     all_ids = rows_impl.unpack_rows(all_packed, all_ptr, all_ln, ld, pad_id, segment_rows=per, segment_stride=capacity, status=ustatus,
                                     **({"u16": True} if u16 else {}))
-    verdict = torch.maximum(all_ext[:, per].max().to(torch.int32).reshape(1), ustatus)
+    verdict = _or_status(all_ext[:, per]) | ustatus
+    _fail_if_too_wide(verdict, elem_bytes)
     if not caller_bound:
         st = int(verdict.item())
         if st:
@@ -159,16 +180,18 @@ def _gather_prepacked(ids, ln, num_graphs, pad_id, packed, rows_impl, stats, wor
         skipped = (all_start < 0) | (all_start + all_ln.clamp(0, ld) > capacity)
         all_start = torch.where(skipped, -1, all_start + seg)
         all_ln = torch.where(skipped, torch.zeros_like(all_ln), all_ln)
-        verdict = all_ext[:, per].max().to(torch.int32).reshape(1)
+        verdict = _or_status(all_ext[:, per])
+        _fail_if_too_wide(verdict, packed.buf.element_size())
         if stats is not None:
             stats.update(bytes_sent_per_rank=capacity * packed.buf.element_size() + per * 8 + (per + 1) * 4, compact=True,
                          elem_bytes=packed.buf.element_size(), capacity=capacity, status=verdict, prepacked=True, as_packed=True)
         return (all_packed, all_start[:num_graphs]), all_ln[:num_graphs]
     ustatus = torch.zeros(1, dtype=torch.int32, device=dev)
-    u16 = packed.buf.dtype == torch.int16
+    u16 = packed.buf.dtype in (torch.int16, torch.uint8)     # (8-bit packed rows come from the 16-bit walk: a 16-bit slab out)
     all_ids = rows_impl.unpack_rows_at(all_packed, all_start, all_ln, ld, pad_id, segment_rows=per, segment_stride=capacity, status=ustatus,
                                        **({"u16": True} if u16 else {}))
-    verdict = torch.maximum(all_ext[:, per].max().to(torch.int32).reshape(1), ustatus)
+    verdict = _or_status(all_ext[:, per]) | ustatus
+    _fail_if_too_wide(verdict, packed.buf.element_size())
     if stats is not None:
         stats.update(bytes_sent_per_rank=capacity * packed.buf.element_size() + per * 8 + (per + 1) * 4, compact=True,
                      elem_bytes=packed.buf.element_size(), capacity=capacity, status=verdict, prepacked=True)

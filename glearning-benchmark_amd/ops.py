@@ -431,6 +431,7 @@ def adjbits(batch: GraphBatch) -> bool:
 
 PACK_STATE_FILL, PACK_STATE_STRIDE, PACK_REGIONS = 16, 16, 64       # include/gtok.h: GTOK_PACK_STATE_*
 PACK_STATE_WORDS = PACK_STATE_FILL + PACK_STATE_STRIDE * PACK_REGIONS
+ID_TOO_WIDE_8 = "an id does not fit 8 bits: use 16-bit packed rows"
 
 
 class PackedRows:
@@ -439,13 +440,22 @@ class PackedRows:
     that did not fit (rows lie in the order their 64-graph units finished, inside up to 64 regions of the buffer that fill side by
     side, not in dataset order - readers go through row_start: ops.unpack_rows_at, ops.collate_packed(buf, row_start, ...)); state
     int64 [PACK_STATE_WORDS]: the status word and the regions' fill marks (include/gtok.h).  Size the buffer as the expected total
-    + a few per cent.  fused: whether the walk kernel itself wrote it (else gtok_sent + gtok_pack_rows_scan did: dataset order)."""
-    __slots__ = ("buf", "row_start", "_ring", "_slot", "capacity", "fused")
+    + a few per cent.  fused: whether the walk kernel itself wrote it (else gtok_sent + gtok_pack_rows_scan did: dataset order).
+    elem_bytes=1 (GTOK_SENT_PACK_U8; with ops.sent(..., u16=True) only): buf is torch.uint8 - one byte per id, rows from multiples
+    of 16 ids, capacity rounded up to 16; status bit 0 then says that an id did not fit 8 bits and the buffer is not to be used
+    (verify() raises).  elem_bytes=None: the slab's width, as `u16` says."""
+    __slots__ = ("buf", "row_start", "_ring", "_slot", "capacity", "fused", "elem_bytes")
     RING = 32          # state blocks (8 KB each) zeroed together: a launch takes the next one instead of paying a memset of its own
 
-    def __init__(self, rows: int, capacity: int, u16: bool, device):
-        self.capacity = max(8, -(-int(capacity) // 8) * 8)
-        self.buf = torch.empty(self.capacity, dtype=torch.int16 if u16 else torch.int32, device=device)
+    def __init__(self, rows: int, capacity: int, u16: bool, device, elem_bytes: Optional[int] = None):
+        if elem_bytes is None:
+            elem_bytes = 2 if u16 else 4
+        if elem_bytes != (2 if u16 else 4) and not (elem_bytes == 1 and u16):
+            raise ValueError("PackedRows: elem_bytes is the slab's id width (2 with u16, else 4), or 1 with u16=True")
+        self.elem_bytes = int(elem_bytes)
+        al = 16 if elem_bytes == 1 else 8
+        self.capacity = max(al, -(-int(capacity) // al) * al)
+        self.buf = torch.empty(self.capacity, dtype={1: torch.uint8, 2: torch.int16, 4: torch.int32}[self.elem_bytes], device=device)
         self.row_start = torch.empty(max(1, int(rows)), dtype=torch.int64, device=device)
         self._ring = torch.zeros((self.RING, PACK_STATE_WORDS), dtype=torch.int64, device=device)
         self._slot = 0
@@ -468,8 +478,14 @@ class PackedRows:
         return self.state
 
     def status(self) -> torch.Tensor:
-        """int32 [1] on the device: the pack_rows status bits of this fill (bit 1: the buffer was too small for some rows)."""
+        """int32 [1] on the device: the pack_rows status bits of this fill (bit 1: the buffer was too small for some rows; bit 0, 8-bit
+        rows only: an id did not fit 8 bits - the buffer is not to be used)."""
         return self.state[0:1].to(torch.int32)
+
+    def verify(self) -> None:
+        """Raise when the last fill met an id that does not fit the buffer's width (status bit 0; one host read)."""
+        if int(self.state[0].item()) & 1:
+            raise _lib.GtokError(ID_TOO_WIDE_8)
 
     def used(self) -> torch.Tensor:
         """int64 scalar on the device: ids the fill took (the regions' fill marks added up; skipped rows included)."""
@@ -480,7 +496,7 @@ def sent(batch: GraphBatch, max_num_nodes: int, max_len: int, seed: int, epoch: 
          num_node_types: int = 0, num_edge_types: int = 0, remap_zinc: bool = False, pad_id: int = SENT_PAD,
          graph_base: int = 0, query: Optional[torch.Tensor] = None,
          ld: Optional[int] = None, out=None, pad: bool = True, epochs: int = 1, u16: bool = False,
-         packed: Optional[PackedRows] = None, slab: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+         packed: Optional[PackedRows] = None, slab: bool = True, check_ids: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
     """SENT trail walk.  Returns (ids int32 [G, ld], len int32 [G]); len > ld flags a too-narrow slab.
     pad=False (GTOK_SENT_NO_PAD): rows are only written up to their length - for consumers that go through `len`
     (ops.collate does); the rest of the slab keeps whatever it held.
@@ -494,7 +510,10 @@ def sent(batch: GraphBatch, max_num_nodes: int, max_len: int, seed: int, epoch: 
     rows), else by gtok_pack_rows_scan behind the walk; either way packed.row_start / packed.state describe the result.
     slab=False (with packed=; GTOK_SENT_PACK_ONLY): the caller reads the packed rows alone - no [K, G, ld] slab is written or
     allocated (the walk stages its rows in a per-device scratch of 64 rows per resident wave: 92 MB on an MI355X whatever K is) and
-    the first return value is None; out=(staging, len) then names the caller's own staging space (or None) and length tensor."""
+    the first return value is None; out=(staging, len) then names the caller's own staging space (or None) and length tensor.
+    packed=PackedRows(..., elem_bytes=1) (with u16=True; GTOK_SENT_PACK_U8): one byte per id in packed.buf.  Whether every id fits
+    is a property of the data, so the status word is read back behind the launch (one host read) and GtokError raised when one
+    did not; check_ids=False - and any launch under stream capture - leaves that to the caller (packed.verify(), packed.status())."""
     _need_gpu(batch.col, "sent")
     dev = batch.device
     K = max(1, int(epochs))
@@ -563,11 +582,22 @@ def sent(batch: GraphBatch, max_num_nodes: int, max_len: int, seed: int, epoch: 
     if packed is not None:
         if _lib.library_version() < 6:
             raise _lib.GtokError(f"the loaded library has ABI version {_lib.library_version()}: packed= needs version 6")
-        if packed.buf.dtype != (torch.int16 if u16 else torch.int32) or packed.row_start.numel() < K * G or packed.buf.device != ln.device:
+        pk8 = packed.buf.dtype == torch.uint8
+        if pk8 and not u16:
+            raise ValueError("packed: 8-bit packed rows go with u16=True (the slab / staging rows stay 16-bit)")
+        if pk8 and _lib.library_version() < 8:
+            raise _lib.GtokError(f"the loaded library has ABI version {_lib.library_version()}: 8-bit packed rows need version 8")
+        if (not pk8 and packed.buf.dtype != (torch.int16 if u16 else torch.int32)) or packed.row_start.numel() < K * G or packed.buf.device != ln.device:
             raise ValueError("packed: a PackedRows of this launch's rows, id width and device")
         packed._fresh_state()
-        if G and ld % (8 if u16 else 4) == 0:
+        if pk8:
+            flags |= _lib.SENT_PACK_U8          # (gtok_sent_packed only: the plain launch below gets p, built before)
+        if G and ld % (16 if pk8 else 8 if u16 else 4) == 0:
             dst, pp = ids, p
+            if pk8 and slab:
+                pp = GtokSentParams(max_num_nodes, int(labeled), num_node_types, num_edge_types, max_len, int(remap_zinc), pad_id,
+                                    flags, seed & (2 ** 64 - 1), epoch & (2 ** 64 - 1), graph_base,
+                                    None if query is None else query.data_ptr(), K, 0)
             if not slab:
                 need = int(lib().gtok_sent_pack_scratch_rows(_stream(dev))) * ld
                 if staging is not None and staging.numel() < need:
@@ -590,13 +620,16 @@ def sent(batch: GraphBatch, max_num_nodes: int, max_len: int, seed: int, epoch: 
             ptr = torch.empty(K * G + 1, dtype=torch.int64, device=dev)
             st = torch.empty(1, dtype=torch.int32, device=dev)
             eb = 2 if u16 else 4
-            check(lib().gtok_pack_rows_scan(ids.data_ptr(), eb, ld, ln.data_ptr(), K * G, 8, eb, packed.buf.data_ptr(), packed.capacity,
+            pb = packed.buf.element_size()          # (1: 8-bit packed rows from the 16-bit slab, 16-id alignment)
+            check(lib().gtok_pack_rows_scan(ids.data_ptr(), eb, ld, ln.data_ptr(), K * G, 16 if pb == 1 else 8, pb, packed.buf.data_ptr(), packed.capacity,
                                             ptr.data_ptr(), st.data_ptr(), _stream(dev)), "gtok_pack_rows_scan")
             # a row the scan skipped keeps its offset in ptr: it is marked -1 here, as the fused route marks it
             skipped = ptr[:-1] + ln.clamp(0, ld) > packed.capacity
             packed.row_start[:K * G].copy_(torch.where(skipped, -1, ptr[:-1]))
             packed.state[PACK_STATE_FILL:PACK_STATE_FILL + 1].copy_(ptr[-1:])
-            packed.state[0:1].copy_(st.to(torch.int64) & 2)
+            packed.state[0:1].copy_(st.to(torch.int64) & (3 if pb == 1 else 2))
+    if packed is not None and packed.buf.dtype == torch.uint8 and check_ids and G and not torch.cuda.is_current_stream_capturing():
+        packed.verify()
     if not slab:
         return None, (ln.view(K, G) if K > 1 else ln.view(G))
     if K > 1:
@@ -693,6 +726,12 @@ def collate(ids: torch.Tensor, ln: torch.Tensor, index: torch.Tensor, pad_id: in
 # packed (ragged) rows: the form token rows take when they leave the GPU (all-gather, D2H)
 # ------------------------------------------------------------------------------------------------
 ROW_ALIGN = 8      # ids: 16-byte aligned row starts at 2 bytes per id (the vector path of pack / unpack)
+ROW_ALIGN_8BIT = 16      # ... at 1 byte per id (elem_bytes=1: the default there)
+_PACKED_DTYPE = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
+
+
+def _row_align(align: Optional[int], elem_bytes: int) -> int:
+    return int(align) if align is not None else (ROW_ALIGN_8BIT if elem_bytes == 1 else ROW_ALIGN)
 
 
 def row_offsets(ln: torch.Tensor, ld: int, align: int = ROW_ALIGN) -> torch.Tensor:
@@ -710,27 +749,29 @@ def row_offsets(ln: torch.Tensor, ld: int, align: int = ROW_ALIGN) -> torch.Tens
 def _pack_verdict(packed, row_ptr, status, cap, what):
     st = int(status.item())
     if st & 1:
-        raise _lib.GtokError(f"{what}: an id does not fit 16 bits; pack with elem_bytes=4")
+        raise _lib.GtokError(f"{what}: " + (ID_TOO_WIDE_8 if packed.element_size() == 1 else "an id does not fit 16 bits; pack with elem_bytes=4"))
     if st & 2:
         raise _lib.GtokError(f"{what}: capacity {cap} is too small for these rows")
     return packed, row_ptr
 
 
-def pack_rows_scan(ids: torch.Tensor, ln: torch.Tensor, elem_bytes: int, capacity: int, align: int = ROW_ALIGN):
+def pack_rows_scan(ids: torch.Tensor, ln: torch.Tensor, elem_bytes: int, capacity: int, align: Optional[int] = None):
     """row_offsets + pack_rows / pack_rows_u16 in ONE pass (gtok_pack_rows_scan): for callers that know a capacity before
     they know the sizes.  ids: the int32 slab or the 16-bit slab (int16 storage).  Returns (packed, row_ptr, status) - nothing
-    waits for the host (status bit 0: an id needs more than 16 bits, bit 1: rows that did not fit `capacity` were skipped)."""
+    waits for the host (status bit 0: an id needs more bits than elem_bytes has, bit 1: rows that did not fit `capacity` were
+    skipped).  elem_bytes=1: uint8 storage; align defaults to 16 ids there, else to ROW_ALIGN."""
     _need_gpu(ids, "pack_rows_scan")
     if ids.dtype not in (torch.int32, torch.int16) or ids.dim() != 2 or not ids.is_contiguous() or ln.dtype != torch.int32 or not ln.is_contiguous():
         raise ValueError("pack_rows_scan expects a contiguous int32 / int16 [rows, ld] slab and contiguous int32 lengths")
     src_bytes = ids.element_size()
-    if elem_bytes not in ((2, 4, 8) if src_bytes == 2 else (2, 4)):
-        raise ValueError("elem_bytes must be 2 or 4 (8 also from a 16-bit slab)")
+    if elem_bytes not in ((1, 2, 4, 8) if src_bytes == 2 else (1, 2, 4)):
+        raise ValueError("elem_bytes must be 1, 2 or 4 (8 also from a 16-bit slab)")
+    align = _row_align(align, elem_bytes)
     dev, (rows, ld) = ids.device, ids.shape
     if int(ln.numel()) != rows:
         raise ValueError("pack_rows_scan: one length per row")
     cap = int(capacity)
-    packed = torch.empty(max(cap, 1), dtype={2: torch.int16, 4: torch.int32, 8: torch.int64}[elem_bytes], device=dev)
+    packed = torch.empty(max(cap, 1), dtype=_PACKED_DTYPE[elem_bytes], device=dev)
     row_ptr = torch.empty(rows + 1, dtype=torch.int64, device=dev)
     status = torch.empty(1, dtype=torch.int32, device=dev)          # (set by the call)
     check(lib().gtok_pack_rows_scan(ids.data_ptr(), src_bytes, ld, ln.data_ptr(), rows, int(align), elem_bytes, packed.data_ptr(), cap,
@@ -739,10 +780,10 @@ def pack_rows_scan(ids: torch.Tensor, ln: torch.Tensor, elem_bytes: int, capacit
 
 
 def pack_rows(ids: torch.Tensor, ln: torch.Tensor, row_ptr: Optional[torch.Tensor] = None, elem_bytes: int = 2,
-              capacity: Optional[int] = None, align: int = ROW_ALIGN, check_status: bool = True):
+              capacity: Optional[int] = None, align: Optional[int] = None, check_status: bool = True):
     """[rows, ld] int32 slab + lengths -> (packed, row_ptr): row r's ids back to back from packed[row_ptr[r]], int16
-    storage (ids 0..65535 kept as their 16 bits) or int32.  capacity: elements to allocate (an all-gather needs the
-    same size on every rank); default = exactly row_ptr[-1] (one host read).  Raises when elem_bytes == 2 and an id
+    storage (ids 0..65535 kept as their 16 bits), int32, or uint8 (elem_bytes=1: ids 0..255, align defaults to 16).  capacity: elements to allocate (an all-gather needs the
+    same size on every rank); default = exactly row_ptr[-1] (one host read).  Raises when elem_bytes is 1 or 2 and an id
     needs more bits, or when `capacity` is too small; check_status=False hands the status tensor back instead
     (packed, row_ptr, status) and leaves the host out of it."""
     _need_gpu(ids, "pack_rows")
@@ -751,36 +792,35 @@ def pack_rows(ids: torch.Tensor, ln: torch.Tensor, row_ptr: Optional[torch.Tenso
     dev, (rows, ld) = ids.device, ids.shape
     if int(ln.numel()) != rows:
         raise ValueError("pack_rows: one length per row")
+    if elem_bytes not in (1, 2, 4):
+        raise ValueError("elem_bytes must be 1, 2 or 4")
+    align = _row_align(align, elem_bytes)
     if row_ptr is None and capacity is not None and _lib.library_version() >= 5:       # sizes not needed first: one pass
         packed, row_ptr, status = pack_rows_scan(ids, ln.contiguous(), elem_bytes, capacity, align)
         return (packed, row_ptr, status) if not check_status else _pack_verdict(packed, row_ptr, status, int(capacity), "pack_rows")
     if row_ptr is None:
         row_ptr = row_offsets(ln, ld, align)
     cap = int(row_ptr[-1]) if capacity is None else int(capacity)
-    packed = torch.empty(max(cap, 1), dtype=torch.int16 if elem_bytes == 2 else torch.int32, device=dev)
+    packed = torch.empty(max(cap, 1), dtype=_PACKED_DTYPE[elem_bytes], device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     check(lib().gtok_pack_rows(ids.data_ptr(), ld, ln.data_ptr(), rows, row_ptr.data_ptr(), elem_bytes, packed.data_ptr(),
                                cap, status.data_ptr(), _stream(dev)), "gtok_pack_rows")
     if not check_status:
         return packed, row_ptr, status
-    st = int(status.item())
-    if st & 1:
-        raise _lib.GtokError("pack_rows: an id does not fit 16 bits; pack with elem_bytes=4")
-    if st & 2:
-        raise _lib.GtokError(f"pack_rows: capacity {cap} is too small for these rows")
-    return packed, row_ptr
+    return _pack_verdict(packed, row_ptr, status, cap, "pack_rows")
 
 
 def pack_rows_u16(ids16: torch.Tensor, ln: torch.Tensor, row_ptr: Optional[torch.Tensor] = None, elem_bytes: int = 2,
-                  capacity: Optional[int] = None, align: int = ROW_ALIGN, check_status: bool = True):
-    """pack_rows reading a 16-bit slab (ops.sent(..., u16=True)): -> (packed, row_ptr) with int16, int32 or int64 storage
-    (elem_bytes 2 / 4 / 8; 8 = the dtype the reference's token tensors have: the packed buffer can leave for the host as
+                  capacity: Optional[int] = None, align: Optional[int] = None, check_status: bool = True):
+    """pack_rows reading a 16-bit slab (ops.sent(..., u16=True)): -> (packed, row_ptr) with uint8, int16, int32 or int64 storage
+    (elem_bytes 1 / 2 / 4 / 8; 1 = ids 0..255, align defaults to 16, raises when an id needs more bits; 8 = the dtype the reference's token tensors have: the packed buffer can leave for the host as
     it is).  check_status=False: (packed, row_ptr, status) and no host read."""
     _need_gpu(ids16, "pack_rows_u16")
     if ids16.dtype != torch.int16 or ids16.dim() != 2 or not ids16.is_contiguous() or ln.dtype != torch.int32:
         raise ValueError("pack_rows_u16 expects a contiguous int16 [rows, ld] slab and int32 lengths")
-    if elem_bytes not in (2, 4, 8):
-        raise ValueError("elem_bytes must be 2, 4 or 8")
+    if elem_bytes not in (1, 2, 4, 8):
+        raise ValueError("elem_bytes must be 1, 2, 4 or 8")
+    align = _row_align(align, elem_bytes)
     dev, (rows, ld) = ids16.device, ids16.shape
     if int(ln.numel()) != rows:
         raise ValueError("pack_rows_u16: one length per row")
@@ -790,15 +830,13 @@ def pack_rows_u16(ids16: torch.Tensor, ln: torch.Tensor, row_ptr: Optional[torch
     if row_ptr is None:
         row_ptr = row_offsets(ln, ld, align)
     cap = int(row_ptr[-1]) if capacity is None else int(capacity)
-    packed = torch.empty(max(cap, 1), dtype={2: torch.int16, 4: torch.int32, 8: torch.int64}[elem_bytes], device=dev)
+    packed = torch.empty(max(cap, 1), dtype=_PACKED_DTYPE[elem_bytes], device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     check(lib().gtok_pack_rows_u16(ids16.data_ptr(), ld, ln.data_ptr(), rows, row_ptr.data_ptr(), elem_bytes, packed.data_ptr(),
                                    cap, status.data_ptr(), _stream(dev)), "gtok_pack_rows_u16")
     if not check_status:
         return packed, row_ptr, status
-    if int(status.item()) & 2:
-        raise _lib.GtokError(f"pack_rows_u16: capacity {cap} is too small for these rows")
-    return packed, row_ptr
+    return _pack_verdict(packed, row_ptr, status, cap, "pack_rows_u16")
 
 
 def unpack_rows(packed: torch.Tensor, row_ptr: Optional[torch.Tensor], ln: torch.Tensor, ld: int, pad_id: int,
@@ -813,8 +851,8 @@ def unpack_rows(packed: torch.Tensor, row_ptr: Optional[torch.Tensor], ln: torch
     _need_gpu(packed, "unpack_rows")
     dev, rows = packed.device, int(ln.numel())
     eb = packed.element_size()
-    if eb not in (2, 4):
-        raise ValueError("unpack_rows expects int16 or int32 storage")
+    if eb not in (1, 2, 4):
+        raise ValueError("unpack_rows expects uint8, int16 or int32 storage")
     want = torch.int16 if u16 else torch.int32
     ids = torch.empty((rows, ld), dtype=want, device=dev) if out is None else out
     if ids.dtype != want:
@@ -835,8 +873,8 @@ def unpack_rows_at(packed: torch.Tensor, row_start: torch.Tensor, ln: torch.Tens
     _need_gpu(packed, "unpack_rows_at")
     dev, rows = packed.device, int(ln.numel())
     eb = packed.element_size()
-    if eb not in (2, 4) or row_start.dtype != torch.int64 or int(row_start.numel()) < rows or not row_start.is_contiguous():
-        raise ValueError("unpack_rows_at expects int16 / int32 storage and one contiguous int64 start per row")
+    if eb not in (1, 2, 4) or row_start.dtype != torch.int64 or int(row_start.numel()) < rows or not row_start.is_contiguous():
+        raise ValueError("unpack_rows_at expects uint8 / int16 / int32 storage and one contiguous int64 start per row")
     want = torch.int16 if u16 else torch.int32
     ids = torch.empty((rows, ld), dtype=want, device=dev) if out is None else out
     if ids.dtype != want:

@@ -276,34 +276,43 @@ def sent_packed(node_ptr: Tensor, edge_ptr: Tensor, rowptr: Tensor, col: Tensor,
                 remap_zinc: bool, pad_id: int, graph_base: int, u16: bool, capacity: int, graph_ids: Optional[Tensor] = None,
                 unit_ptr: Optional[Tensor] = None, unit_info: Optional[Tensor] = None, rowptr8: Optional[Tensor] = None,
                 col8: Optional[Tensor] = None, adj_rows: Optional[Tensor] = None, adj_planes: Optional[Tensor] = None,
-                lane_order: Optional[Tensor] = None, layout: Optional[List[int]] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+                lane_order: Optional[Tensor] = None, layout: Optional[List[int]] = None,
+                elem_bytes: int = 2) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
     """gtok_sent_packed with GTOK_SENT_PACK_ONLY (ABI v6): the walk of `epochs` epochs packs its rows itself and writes no slab ->
     (len int32 [epochs * G], packed [capacity rounded up to 8] ids - int16 storage when u16 -, row_start int64 [epochs * G], state
     int64 [2] = (ids used, status bits: 2 = rows did not fit)).  Readers: gtok::unpack_rows_at, gtok::collate_packed with row_ptr =
-    row_start.  Batches another kernel walks go through a temporary slab and gtok_pack_rows_scan (same outputs, dataset order)."""
+    row_start.  Batches another kernel walks go through a temporary slab and gtok_pack_rows_scan (same outputs, dataset order).
+    elem_bytes=1 (with u16; GTOK_SENT_PACK_U8): packed is uint8 [capacity rounded up to 16], one byte per id, rows from multiples of
+    16; status bit 0 (value 1) in state[1] then says that an id did not fit 8 bits and the buffer is not to be used (nothing is
+    read back here).  Any other value: the slab's width, as `u16` says."""
+    if elem_bytes == 1 and not u16:
+        raise ValueError("sent_packed: elem_bytes=1 goes with u16=True")
     b = _sent_batch(node_ptr, edge_ptr, rowptr, col, nattr, eattr, max_nodes, max_edges, graph_ids, unit_ptr, unit_info, rowptr8, col8,
                     adj_rows, adj_planes, lane_order, layout)
     rows = b.num_graphs * max(1, epochs)
-    pk = _ops.PackedRows(rows, capacity, u16, b.device)
+    pk = _ops.PackedRows(rows, capacity, u16, b.device, elem_bytes=1 if elem_bytes == 1 else None)
     _, ln = _ops.sent(b, max_num_nodes, max_len, seed, epoch, labeled=labeled, num_node_types=num_node_types,
                       num_edge_types=num_edge_types, remap_zinc=remap_zinc, pad_id=pad_id, graph_base=graph_base,
-                      query=query, ld=ld, epochs=epochs, u16=u16, packed=pk, slab=False)
+                      query=query, ld=ld, epochs=epochs, u16=u16, packed=pk, slab=False, check_ids=False)
     return ln.reshape(-1), pk.buf, pk.row_start[:rows], torch.stack([pk.used(), pk.state[0]])
 
 
 def _sent_packed_fake(node_ptr, edge_ptr, rowptr, col, nattr, eattr, query, max_nodes, max_edges, max_num_nodes, max_len, ld, seed,
                       epoch, epochs, labeled, num_node_types, num_edge_types, remap_zinc, pad_id, graph_base, u16, capacity, graph_ids=None,
-                      unit_ptr=None, unit_info=None, rowptr8=None, col8=None, adj_rows=None, adj_planes=None, lane_order=None, layout=None):
+                      unit_ptr=None, unit_info=None, rowptr8=None, col8=None, adj_rows=None, adj_planes=None, lane_order=None, layout=None,
+                      elem_bytes=2):
     rows = (node_ptr.shape[0] - 1) * max(1, epochs)
-    cap = max(8, -(-capacity // 8) * 8)
-    return (node_ptr.new_empty((rows,), dtype=torch.int32), node_ptr.new_empty((cap,), dtype=torch.int16 if u16 else torch.int32),
+    al = 16 if elem_bytes == 1 else 8
+    cap = max(al, -(-capacity // al) * al)
+    return (node_ptr.new_empty((rows,), dtype=torch.int32),
+            node_ptr.new_empty((cap,), dtype=torch.uint8 if elem_bytes == 1 else torch.int16 if u16 else torch.int32),
             node_ptr.new_empty((rows,), dtype=torch.int64), node_ptr.new_empty((2,), dtype=torch.int64))
 
 
 _FRAG.define("sent_packed(Tensor node_ptr, Tensor edge_ptr, Tensor rowptr, Tensor col, Tensor? nattr, Tensor? eattr, Tensor? query, int max_nodes, "
              "int max_edges, int max_num_nodes, int max_len, int ld, int seed, int epoch, int epochs, bool labeled, int num_node_types, "
              "int num_edge_types, bool remap_zinc, int pad_id, int graph_base, bool u16, int capacity, " + _PREPARED_SCHEMA
-             + ") -> (Tensor, Tensor, Tensor, Tensor)")
+             + ", int elem_bytes=2) -> (Tensor, Tensor, Tensor, Tensor)")
 _FRAG.impl("sent_packed", sent_packed, "CUDA")
 torch.library.register_fake("gtok::sent_packed", _sent_packed_fake, lib=_FRAG)
 
@@ -491,7 +500,7 @@ def pack_rows(ids: Tensor, lens: Tensor, row_ptr: Tensor, elem_bytes: int, capac
 
 @pack_rows.register_fake
 def _(ids, lens, row_ptr, elem_bytes, capacity):
-    return (ids.new_empty((max(capacity, 1),), dtype=torch.int16 if elem_bytes == 2 else torch.int32),
+    return (ids.new_empty((max(capacity, 1),), dtype={1: torch.uint8, 2: torch.int16}.get(elem_bytes, torch.int32)),
             ids.new_empty((1,), dtype=torch.int32))
 
 
@@ -504,7 +513,7 @@ def pack_rows_u16(ids16: Tensor, lens: Tensor, row_ptr: Tensor, elem_bytes: int,
 
 @pack_rows_u16.register_fake
 def _(ids16, lens, row_ptr, elem_bytes, capacity):
-    return (ids16.new_empty((max(capacity, 1),), dtype={2: torch.int16, 4: torch.int32, 8: torch.int64}[elem_bytes]),
+    return (ids16.new_empty((max(capacity, 1),), dtype={1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[elem_bytes]),
             ids16.new_empty((1,), dtype=torch.int32))
 
 
@@ -516,7 +525,7 @@ def pack_rows_scan(ids: Tensor, lens: Tensor, elem_bytes: int, capacity: int, al
 
 @pack_rows_scan.register_fake
 def _(ids, lens, elem_bytes, capacity, align):
-    return (ids.new_empty((max(capacity, 1),), dtype={2: torch.int16, 4: torch.int32, 8: torch.int64}[elem_bytes]),
+    return (ids.new_empty((max(capacity, 1),), dtype={1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[elem_bytes]),
             ids.new_empty((lens.shape[0] + 1,), dtype=torch.int64), ids.new_empty((1,), dtype=torch.int32))
 
 

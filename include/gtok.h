@@ -394,7 +394,7 @@ int gtok_sent(const gtok_csr *g, const gtok_sent_params *p, int32_t *out_ids,
 
 /* gtok_sent whose walk ALSO appends every row to a packed buffer (ABI v6): the payload of the compact all-gather and of the
  * per-epoch D2H copy without a second pass over the rows.  `packed` holds `capacity` ids of the slab's width (16-bit with
- * GTOK_SENT_U16, else 32-bit).  The library cuts it into R <= GTOK_PACK_REGIONS equal regions of (capacity / R rounded down to a
+ * GTOK_SENT_U16, else 32-bit; one byte per id with GTOK_SENT_PACK_U8, below).  The library cuts it into R <= GTOK_PACK_REGIONS equal regions of (capacity / R rounded down to a
  * multiple of 8) ids, each with a fill mark of its own - one mark for all 64-graph units costs as much as the walk - and deals
  * the units to the regions so that they fill evenly (R = the largest power of two that leaves every region >= 64 (unit, epoch)
  * pairs; a ZINC-full epoch: 32 regions that end within 1 % of each other): size `capacity` as the expected total + a few
@@ -411,6 +411,15 @@ int gtok_sent(const gtok_csr *g, const gtok_sent_params *p, int32_t *out_ids,
                                 [K, G, ld] slab: every resident wave reuses its 64 rows for all of its units, the row stores stay in
                                 the caches and K epochs need 92 MB of staging on an MI355X instead of K slabs.  Implies
                                 GTOK_SENT_NO_PAD.                                                                              */
+#define GTOK_SENT_PACK_U8 8   /* gtok_sent_params.flags, gtok_sent_packed only and only together with GTOK_SENT_U16 (ABI v8): `packed` holds
+                                `capacity` ONE-byte ids (the slab, or the GTOK_SENT_PACK_ONLY staging rows, stay 16-bit).  row_start, the
+                                fill marks and capacity count ids = bytes; rows start on 16-byte boundaries = multiples of 16 ids, a
+                                region is (capacity / R rounded down to a multiple of 16) ids, the bytes between a row's end and the
+                                next boundary are zeros.  An id that does not fit 8 bits raises bit 0 (value 1) of state[0]: the
+                                buffer is not to be used, walk again with 16-bit packed rows (type attributes are passed through
+                                un-clamped, so the id space is a property of the data, not of the parameters).  Needs ld % 16 == 0
+                                (a staged row is a whole number of PAIRS of 16-byte pieces; GTOK_E_INVAL otherwise); ld <= 2040 as
+                                for 16-bit rows.  gtok_sent refuses the flag (GTOK_E_INVAL).                                       */
 #define GTOK_PACK_REGIONS 64
 #define GTOK_PACK_STATE_FILL 16    /* the fill marks start one cache line behind the status word ... */
 #define GTOK_PACK_STATE_STRIDE 16  /* ... and keep a cache line each                                   */
@@ -459,14 +468,16 @@ int gtok_parse_graph_text(const uint8_t *bytes, const int64_t *text_ptr, int32_t
 
 /* ---- packed (ragged) rows -------------------------------------------------------------------------------------
  * The padded slab is the documented output of every tokenizer entry point; more than half of a ZINC slab is padding
- * and every id fits 16 bits.  The packed form holds row r's n_r = min(len[r], ld) ids contiguously, `elem_bytes`
- * (2 or 4) bytes each, from element row_ptr[r] of `packed`.
+ * and every id fits 16 bits (8 bits for ZINC molecules).  The packed form holds row r's n_r = min(len[r], ld) ids contiguously,
+ * `elem_bytes` (1, 2 or 4; 1 since ABI v8, accepted by every entry point of this block) bytes each, from element row_ptr[r] of
+ * `packed`.
  *
  * gtok_row_offsets: row_ptr[0] = 0, row_ptr[r + 1] = row_ptr[r] + round_up(n_r, align) for r < num_rows (int64
- * [num_rows + 1], align a power of two: 8 keeps every row start 16-byte aligned at 2 bytes per id - the fast path of
- * pack / unpack - 1 packs tightly).  Three small launches, no workspace.
+ * [num_rows + 1], align a power of two: 8 keeps every row start 16-byte aligned at 2 bytes per id, 16 at 1 byte per id - the
+ * fast path of pack / unpack - 1 packs tightly).  Three small launches, no workspace.
  * gtok_pack_rows: slab -> packed, a buffer of `capacity` elements.  status[0] (zeroed by the caller) gets bit 0 when
- * elem_bytes == 2 and an id does not fit 16 bits (pack again with elem_bytes == 4), bit 1 when capacity <
+ * an id does not fit the packed width - elem_bytes == 2 and an id beyond 16 bits of an int32 slab, or elem_bytes == 1 and an id
+ * beyond 8 bits of either slab: the buffer is not to be used, pack again one width up -, bit 1 when capacity <
  * row_ptr[num_rows] (rows that do not fit are skipped, nothing is written out of bounds).
  * gtok_unpack_rows: packed -> [num_rows, ld] slab, pad_id behind every row.  segment_rows > 0: the packed buffer is
  * the concatenation of equally sized segments - what an all-gather of per-rank buffers of segment_stride elements
@@ -482,7 +493,7 @@ int gtok_parse_graph_text(const uint8_t *bytes, const int64_t *text_ptr, int32_t
  * (a rank whose rows did not fit the caller-given capacity skipped them in gtok_pack_rows, status bit 1) is written as
  * all pad and, when `status` is not NULL, flagged there (bit 1) - gtok_unpack_rows_checked is gtok_unpack_rows with that
  * status word and the total number of elements `packed` holds (0 = unknown) as further bounds.
- * gtok_pack_rows_u16: gtok_pack_rows reading a GTOK_SENT_U16 slab; elem_bytes 2, 4 or 8 (8: int64 ids, the dtype the
+ * gtok_pack_rows_u16: gtok_pack_rows reading a GTOK_SENT_U16 slab; elem_bytes 1, 2, 4 or 8 (8: int64 ids, the dtype the
  * reference's tensors have - the D2H copy behind TokenizedGraphDataset.__getitem__ needs no widening pass).           */
 int gtok_row_offsets(const int32_t *len, int64_t num_rows, int32_t ld, int32_t align, int64_t *row_ptr, void *stream);
 int gtok_pack_rows(const int32_t *ids, int32_t ld, const int32_t *len, int64_t num_rows, const int64_t *row_ptr,
@@ -639,8 +650,9 @@ const char *gtok_ibtt_zinc_kernel_name(const gtok_csr *g);
  * mirrors - a binding checks it before passing structs; 3 adds the packed-row entry points; 4: gtok_sent_params carries
  * epoch_count, GTOK_SENT_U16, the strided / checked packed-row readers; 5 adds gtok_csr_check / gtok_csr_lane_sort -
  * structs unchanged; 6 adds gtok_sent_packed / GTOK_SENT_PACK_ONLY / gtok_unpack_rows_at / GTOK_E_UNSUPPORTED - structs
- * unchanged; 7 adds gtok_csr_from_coo - structs unchanged) and build target string ("gfx950").                     */
-#define GTOK_ABI_VERSION 7
+ * unchanged; 7 adds gtok_csr_from_coo - structs unchanged; 8 adds elem_bytes == 1 to the packed-row entry points and
+ * GTOK_SENT_PACK_U8 - structs unchanged) and build target string ("gfx950").                                        */
+#define GTOK_ABI_VERSION 8
 int gtok_version(void);
 const char *gtok_target(void);
 
