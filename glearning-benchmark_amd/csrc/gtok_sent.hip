@@ -110,8 +110,14 @@ static int sent_impl(const gtok_csr *g, const gtok_sent_params *p, int32_t *out_
   const int maxe = g->max_edges > 0 ? g->max_edges : 1;
   const int which = choose_sent_kernel(g, p);
   if (which < 0) return GTOK_E_INVAL;       // a reordered batch the lane-per-graph kernel cannot take
-  if (pd) {   // rows appended to a packed buffer by the walk itself: the lane-per-graph molecule kernel, rows that start on 16-byte boundaries
-    if (which != 0) return GTOK_E_UNSUPPORTED;
+  if (pd) {   // rows appended to a packed buffer by the walk itself: the two lane-per-graph kernels, rows that start on 16-byte boundaries
+    if (which != 0 && which != 3) return GTOK_E_UNSUPPORTED;
+    if (which == 3) {
+      // the bit-matrix kernel packs where regions mean something (>= GTOK_BLANE_MIN_GRAPHS walks, chosen or pinned), at the slab's id
+      // width (position ids reach 6 + 255 in its batches: no 8-bit rows) and with a row's pieces counted in 8 bits; everything
+      // else keeps the two-call route (gtok_sent + gtok_pack_rows_scan), which callers take on this code
+      if ((int64_t)g->num_graphs * K < GTOK_BLANE_MIN_GRAPHS || pk8 || ld > (u16 ? 2040 : 1020)) return GTOK_E_UNSUPPORTED;
+    }
     if (!pd->packed || !pd->row_start || !pd->state || pd->capacity < 0) return GTOK_E_INVAL;
     if (ld > (u16 ? 2040 : 1020)) return GTOK_E_TOO_LARGE;    // (a row's 16-byte pieces are counted in 8 bits)
     if (ld % (pk8 ? 16 : u16 ? 8 : 4) != 0 || (reinterpret_cast<uintptr_t>(out_ids) & 15u) || (reinterpret_cast<uintptr_t>(pd->packed) & 15u)) return GTOK_E_INVAL;
@@ -127,6 +133,12 @@ static int sent_impl(const gtok_csr *g, const gtok_sent_params *p, int32_t *out_
     a.epochs = K;
     a.pad_nt = pad_nt;
     a.prio = 1;
+    a.pack_out = pd ? pd->packed : nullptr;
+    a.pack_start = pd ? pd->row_start : nullptr;
+    a.pack_state = pd ? reinterpret_cast<unsigned long long *>(pd->state) : nullptr;
+    a.pack_region_cap = 0; a.pack_regions = 1;
+    a.pack_scratch = pd && (p->flags & GTOK_SENT_PACK_ONLY) ? 1 : 0;
+    if (a.pack_scratch) a.p.flags |= GTOK_SENT_NO_PAD;                   // (nobody reads the staging rows' tails)
     if (const char *cs = std::getenv("GTOK_BLANE_PRIO")) a.prio = cs[0] != '0';   // tuning knob
     const bool p4 = g->adj_max_degree <= 15;
     typedef void (*KF)(const SentBLaneArgs);
@@ -136,6 +148,14 @@ static int sent_impl(const gtok_csr *g, const gtok_sent_params *p, int32_t *out_
             : (p4 ? (KF)sent_blane_kernel<4, 4, U> : (KF)sent_blane_kernel<4, 8, U>))
     KF kern = u16 ? GTOK_BLANE_K(true) : GTOK_BLANE_K(false);
 #undef GTOK_BLANE_K
+    if (pd) {   // gtok_sent_packed: the instantiations that append to the packed buffer
+#define GTOK_BLANE_KP(U)                                                                                            \
+  (W == 1 ? (p4 ? (KF)sent_blane_kernel<1, 4, U, true> : (KF)sent_blane_kernel<1, 8, U, true>)                     \
+   : W == 2 ? (p4 ? (KF)sent_blane_kernel<2, 4, U, true> : (KF)sent_blane_kernel<2, 8, U, true>)                   \
+            : (p4 ? (KF)sent_blane_kernel<4, 4, U, true> : (KF)sent_blane_kernel<4, 8, U, true>))
+      kern = u16 ? GTOK_BLANE_KP(true) : GTOK_BLANE_KP(false);
+#undef GTOK_BLANE_KP
+    }
     const size_t lds = (size_t)5120 * W;   // 20 W dwords per lane (gtok_sent_blane.hpp)
     const int dev = device_scope.dev, ncu = device_cu_count(dev);
     // one workgroup per CU: 8 waves at W = 4 (160 KB of LDS, 2 per SIMD: the register file holds no more), else 16
@@ -144,6 +164,13 @@ static int sent_impl(const gtok_csr *g, const gtok_sent_params *p, int32_t *out_
     if (!raise_lds_limit(reinterpret_cast<const void *>(kern), dev)) return GTOK_E_LAUNCH;
     const int vun = a.units * K;
     const int nb = vun < ncu ? vun : ncu;   // every CU, also when some of its waves stay without a unit
+    if (pd) {   // regions of the packed buffer: the molecule kernel's rule (pairs are dealt unit-major and lane_order stores the units by
+                // expected length, so vu mod regions hands every region the same mix); staging: 64 rows x nw <= 16 waves x nb <= CUs
+      int m = GTOK_PACK_REGIONS;
+      while (m > 1 && vun < 64 * m) m >>= 1;
+      a.pack_regions = m;
+      a.pack_region_cap = (pd->capacity / m) & ~(int64_t)7;
+    }
     if (2 * nb > kSlotInts) return GTOK_E_TOO_LARGE;      // (two ticket words per workgroup in one counter block: 528 CUs)
     // unit-major always: the K walks of a unit fetch the same adjacency rows at about the same time (L2 hits on the one HBM read
     // of a step) - 125 k ER graphs x 8 epochs: 0.356 ms per epoch against 0.404 epoch-major (0.49 for one epoch per launch)

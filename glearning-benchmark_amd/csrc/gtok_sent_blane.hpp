@@ -36,6 +36,13 @@ struct SentBLaneArgs {
   int *tickets;      // 2 ints per workgroup in device memory, zero between launches: [2 b] the ticket of the pairs beyond the first
                      // round, [2 b + 1] the waves of workgroup b that are through (the last one re-arms both).  Round 5: the LDS is
                      // full to the last byte (8 x 20 KB at W = 4), the counter moved out; a draw costs ~1 us once per ~400 us unit
+  // gtok_sent_packed (the PACK instantiations only; NULL / 0 otherwise): as in SentLaneArgs, same format, same readers
+  void *pack_out;
+  int64_t *pack_start;              // [K * G] first id of row (epoch, graph) in pack_out; -1: did not fit
+  unsigned long long *pack_state;   // GTOK_PACK_STATE_WORDS words: [0] status bits, [FILL + STRIDE * r] ids used in region r
+  int64_t pack_region_cap;          // ids per region (a multiple of 8)
+  int pack_regions;                 // a power of two <= GTOK_PACK_REGIONS
+  int pack_scratch;                 // GTOK_SENT_PACK_ONLY: `out` is staging space, 64 rows per resident wave
 };
 
 struct __attribute__((aligned(16))) U64x2 { uint64_t a, b; };
@@ -45,7 +52,9 @@ struct __attribute__((aligned(16))) U64x2 { uint64_t a, b; };
 constexpr int kBlaneConv = GTOK_BLANE_CONV;   // bracket members taken to visit-index space per loop iteration
 
 // U16: the GTOK_SENT_U16 slab - rows of 16-bit ids, the token windows stored as they stand
-template <int W, int P, bool U16>
+// PACK: gtok_sent_packed - a finished unit's rows are also appended to the packed buffer (instantiations of their own: the plain
+// ones do not carry a line of it)
+template <int W, int P, bool U16, bool PACK = false>
 __global__ void __launch_bounds__(W == 4 ? 512 : 1024) sent_blane_kernel(const SentBLaneArgs a) {
   using out_t = typename std::conditional<U16, uint16_t, int32_t>::type;
   constexpr int EV = U16 ? 8 : 4;            // ids per 16-byte store
@@ -144,7 +153,11 @@ __global__ void __launch_bounds__(W == 4 ? 512 : 1024) sent_blane_kernel(const S
 
     const uint64_t gid = (uint64_t)(a.p.graph_base + g);
     const uint32_t gid_lo = (uint32_t)gid, gid_hi = (uint32_t)(gid >> 32);
-    out_t *__restrict__ orow = out_base + (row0 + g) * ld;
+    // (gtok_sent_packed with GTOK_SENT_PACK_ONLY: `out` is only this wave's staging area - 64 rows that every unit of the wave
+    // writes again; out_len and pack_start keep the dataset index)
+    int64_t srow = row0 + g;
+    if constexpr (PACK) { if (a.pack_scratch) srow = (int64_t)(((int)blockIdx.x * nwaves + wave) * 64 + lane); }
+    out_t *__restrict__ orow = out_base + srow * ld;
     uint64_t vis[W], rowc[W];
 #pragma unroll
     for (int w = 0; w < W; ++w) { vis[w] = 0; rowc[w] = 0; }
@@ -486,6 +499,89 @@ __global__ void __launch_bounds__(W == 4 ? 512 : 1024) sent_blane_kernel(const S
         }
       }
     }
+    // ---- gtok_sent_packed: the unit's rows are appended to the packed buffer as well, each from a 16-byte boundary - the format of
+    // gtok_sent_lane.hpp (regions with a fill mark each, pair vu appends to region vu mod regions, ONE atomic add per unit issued
+    // behind the copy's first loads, row_start says where each row went), so that every reader works unchanged.  This is a second
+    // copy of that kernel's append on purpose: shared text would have to be called from sent_lane_kernel too, every instantiation
+    // of which sits at 128 registers - its register allocation is the one thing this code must not move.
+    // What differs: rows have up to ld / EV <= 255 pieces (76 at ld = 608; the molecule rows <= 22), so the sweep loop runs
+    // several times; there is no LDS to spare (row index and (offset, piece count) travel by ds_bpermute here too); and the copy
+    // stands BEFORE the pad tails, whose stores then leave behind it without anybody waiting for them.
+    // Coherence: the rows read below were written by other lanes of this wave with PLAIN stores (store_win, store_tok4 and the
+    // scalar tail loop above) - a CU's loads and stores go through its one vector cache, which keeps store -> load coherent per
+    // address (gtok_sent_lane.hpp).  Only the pad tails may be non-temporal, and they start at `padfrom`, which the copy never
+    // reaches: its last piece ends at np * EV <= padfrom (the row's end above is written out to a 16-token boundary, or to a whole
+    // piece on the query / odd path), so the alignment tail of a packed row holds pad ids.  Keep the row's own stores plain.
+#ifdef GTOK_PHASE_TIMING
+    [[maybe_unused]] uint64_t pkt[2] = {0, 0};      // gtok_sent_packed: cycles until the atomic answered / of the copy
+#endif
+    if constexpr (PACK) {
+#ifdef GTOK_PHASE_TIMING
+      const uint64_t tp0 = __builtin_amdgcn_s_memtime();
+      uint64_t tp1 = tp0;
+#endif
+      const int nid = valid ? min(tot, ld) : 0;     // (invalid lanes of the last unit: no pieces)
+      const int np = (nid + EV - 1) / EV;
+      const int inc = wave_incl_scan_dpp(np);
+      const int total = __builtin_amdgcn_readlane(inc, kWave - 1);
+      const int region = vu & (a.pack_regions - 1);
+      const int cnt = min(64, G - unit * 64);
+      const int q = lane & 15, qg = lane >> 4;
+      // (np <= 255: the launcher checks ld; the offset stays below 64 * 255 pieces)
+      const int my_row = valid ? (int)srow : -1, my_offnp = ((inc - np) << 8) | np;
+      const int my_row0 = __builtin_amdgcn_readfirstlane((int)srow);               // (a row of this unit: lane 0 is always valid)
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      // A sweep = 16-byte piece 16 sweep + q of every row, in two batches of eight passes of four rows (32 registers of loads)
+      constexpr int KF = 8;
+      bool fits = true, placed = false;
+      gtok_v4i *dstbase = nullptr;
+      for (int sweep = 0;; ++sweep) {
+        const int t = sweep * 16 + q;
+        _Pragma("clang loop unroll(disable)")
+        for (int b0 = 0; b0 < 16; b0 += KF) {
+          if (b0 * 4 >= cnt) break;
+          gtok_v4i v[KF];
+          int doff[KF];
+#pragma unroll
+          for (int k = 0; k < KF; ++k) {
+            const int rn = ((b0 + k) * 4 + qg) << 2;
+            const int r_idx = __builtin_amdgcn_ds_bpermute(rn, my_row);
+            const int r_on = __builtin_amdgcn_ds_bpermute(rn, my_offnp);
+            const bool on = r_idx >= 0 && t < (r_on & 255);
+            doff[k] = on ? (r_on >> 8) + t : -1;
+            // (an address is always formed - a row of this unit for the lanes that have nothing to fetch - so that the loads leave
+            // back to back instead of each behind a branch of its own)
+            v[k] = reinterpret_cast<const gtok_v4i *>(out_base + (int64_t)(on ? r_idx : my_row0) * ld)[on ? t : 0];
+          }
+          if (!placed) {
+            // the fill mark is asked BEHIND the first loads: one wait covers the unit's row stores draining, the loads and the atomic
+            placed = true;
+            unsigned long long base = 0;
+            if (lane == 0)
+              base = __hip_atomic_fetch_add(a.pack_state + GTOK_PACK_STATE_FILL + GTOK_PACK_STATE_STRIDE * region, (unsigned long long)total * EV,
+                                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            base = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32)) << 32) |
+                   (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
+            fits = base + (unsigned long long)total * EV <= (unsigned long long)a.pack_region_cap;
+            const int64_t rstart = (int64_t)region * a.pack_region_cap + (int64_t)base;
+            dstbase = reinterpret_cast<gtok_v4i *>(reinterpret_cast<out_t *>(a.pack_out) + rstart);
+            if (valid) a.pack_start[row0 + g] = fits ? rstart + (int64_t)(inc - np) * EV : (int64_t)-1;
+            if (!fits && lane == 0 && total > 0) atomicOr(a.pack_state, 2ull);
+#ifdef GTOK_PHASE_TIMING
+            tp1 = __builtin_amdgcn_s_memtime();
+#endif
+          }
+          if (fits) {
+#pragma unroll
+            for (int k = 0; k < KF; ++k) if (doff[k] >= 0) dstbase[doff[k]] = v[k];
+          }
+        }
+        if (__ballot(np > 16 * (sweep + 1)) == 0) break;
+      }
+#ifdef GTOK_PHASE_TIMING
+      pkt[0] = tp1 - tp0; pkt[1] = __builtin_amdgcn_s_memtime() - tp1;
+#endif
+    }
     // ---- pad tails: four rows per pass, 16 lanes x 16-byte stores on each (rows of a unit need not be neighbours)
     if (!no_pad) {
       auto pad_tails = [&](auto nt_tag) __attribute__((always_inline)) {
@@ -513,10 +609,11 @@ __global__ void __launch_bounds__(W == 4 ? 512 : 1024) sent_blane_kernel(const S
 #ifdef GTOK_PHASE_TIMING
     GTOK_PT(4)
     if (!U16 && lane == 0 && ld >= 16) {
-      int32_t *row = a.out + (row0 + g) * ld + ld - 8;
+      int32_t *row = a.out + srow * ld + ld - 8;
       row[0] = (int32_t)pt[0]; row[1] = (int32_t)pt[1]; row[2] = (int32_t)pt[2]; row[3] = (int32_t)pt[3]; row[4] = (int32_t)pt[4];
       row[5] = (int32_t)uni(pt_steps); row[6] = (int32_t)((uni(pt_it1) << 16) | uni(pt_it2));
       row[7] = (int32_t)((uint32_t)__builtin_amdgcn_s_memrealtime() - pt_rt0);
+      if (PACK) { row[5] = (int32_t)pkt[0]; row[6] = (int32_t)pkt[1]; }   // gtok_sent_packed: instead of the step / iteration counts (slot 4 includes both)
     }
 #endif
     // ---- the next pair

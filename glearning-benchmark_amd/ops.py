@@ -435,7 +435,8 @@ ID_TOO_WIDE_8 = "an id does not fit 8 bits: use 16-bit packed rows"
 
 
 class PackedRows:
-    """The packed twin of a SENT launch's rows (ops.sent(..., packed=PackedRows(...)): gtok_sent_packed).  buf: `capacity` ids of
+    """The packed twin of a SENT launch's rows (ops.sent(..., packed=PackedRows(...)): gtok_sent_packed - the walk of either
+    lane-per-graph kernel, sent_lane_kernel or sent_blane_kernel, packs; other batches go through gtok_pack_rows_scan).  buf: `capacity` ids of
     the slab's width, every row from a 16-byte boundary; row_start int64 [rows]: where row (epoch, graph) starts in buf, -1 for a row
     that did not fit (rows lie in the order their 64-graph units finished, inside up to 64 regions of the buffer that fill side by
     side, not in dataset order - readers go through row_start: ops.unpack_rows_at, ops.collate_packed(buf, row_start, ...)); state
@@ -506,10 +507,12 @@ def sent(batch: GraphBatch, max_num_nodes: int, max_len: int, seed: int, epoch: 
     u16=True (GTOK_SENT_U16): the slab holds 16-bit ids (torch.int16 storage, to be read as unsigned: every SENT id fits) -
     half the bytes; readers: ops.collate_packed / ops.unpack_rows with row_ptr=None, ops.pack_rows_u16.
     packed=PackedRows(K * G, capacity, u16, device): the rows are ALSO appended to packed.buf (a fresh fill: its state is
-    zeroed first) - by the walk kernel itself where the batch runs sent_lane_kernel (gtok_sent_packed: no second pass over the
-    rows), else by gtok_pack_rows_scan behind the walk; either way packed.row_start / packed.state describe the result.
+    zeroed first) - by the walk kernel itself where the batch runs sent_lane_kernel, or sent_blane_kernel with >= 20,000 walks
+    (graphs x epochs), 16- / 32-bit packed ids and ld <= 2040 / 1020 (gtok_sent_packed: no second pass over the rows), else by
+    gtok_pack_rows_scan behind the walk; either way packed.row_start / packed.state describe the result and packed.fused says which.
     slab=False (with packed=; GTOK_SENT_PACK_ONLY): the caller reads the packed rows alone - no [K, G, ld] slab is written or
-    allocated (the walk stages its rows in a per-device scratch of 64 rows per resident wave: 92 MB on an MI355X whatever K is) and
+    allocated (the walk stages its rows in a per-device scratch of 64 rows per resident wave: 262,144 rows x ld ids on an MI355X whatever K
+    is - 92 MB at ZINC's ld 176, 319 MB at config 5's ld 608) and
     the first return value is None; out=(staging, len) then names the caller's own staging space (or None) and length tensor.
     packed=PackedRows(..., elem_bytes=1) (with u16=True; GTOK_SENT_PACK_U8): one byte per id in packed.buf.  Whether every id fits
     is a property of the data, so the status word is read back behind the launch (one host read) and GtokError raised when one

@@ -101,8 +101,12 @@ extern "C" {
                                    "sent_blane_kernel", "ibtt_zinc_lane_kernel", gtok_pack_rows_scan) keep one per captured launch for as long as the capturing graph
                                    (and the executable graphs made from it) exist - destroying a graph returns its blocks   */
 
-#define GTOK_E_UNSUPPORTED (-6) /* the request is valid but not for the kernel this batch runs (gtok_sent_packed on a batch that
-                                   gtok_sent_kernel_name() does not answer "sent_lane_kernel" for): use the two-call route    */
+#define GTOK_E_UNSUPPORTED (-6) /* the request is valid but not for the kernel this batch runs: gtok_sent_packed on a batch that
+                                   gtok_sent_kernel_name() answers neither "sent_lane_kernel" nor "sent_blane_kernel<W=..>" for,
+                                   or a "sent_blane_kernel" batch of fewer than 20,000 walks (graphs x epochs), with
+                                   GTOK_SENT_PACK_U8, or with ld > 2040 (1020 at 32 bits).  Nothing was launched or written:
+                                   use the two-call route (gtok_sent + gtok_pack_rows_scan).  Still ABI version 8: callers
+                                   learn what a library packs in the walk from this code                                       */
 
 #define GTOK_MAX_NODES 512 /* SENT adjacency bit-matrix rows per wave (LDS)  */
 
@@ -404,8 +408,14 @@ int gtok_sent(const gtok_csr *g, const gtok_sent_params *p, int32_t *out_ids,
  * `packed`: rows start on 16-byte boundaries and lie in the order in which the units finished, NOT in dataset order - readers go
  * through row_start (gtok_unpack_rows_at, gtok_collate_packed with row_ptr = row_start).  Row r holds min(out_len[r], ld) ids;
  * the slab itself is written as gtok_sent writes it (pass GTOK_SENT_NO_PAD when nobody reads its pad tails).  Needs ld % 8 == 0
- * (% 4 for 32-bit ids), 16-byte aligned out_ids / packed, and a batch that runs the lane-per-graph molecule kernel (else
- * GTOK_E_UNSUPPORTED, nothing is launched: call gtok_sent + gtok_pack_rows_scan).                                           */
+ * (% 4 for 32-bit ids), 16-byte aligned out_ids / packed (else GTOK_E_INVAL), and a batch that runs one of the two lane-per-graph
+ * kernels: the molecule kernel (sent_lane_kernel; ld <= 2040 / 1020, wider: GTOK_E_TOO_LARGE), or the bit-matrix kernel
+ * (sent_blane_kernel: unlabelled graphs of up to 256 nodes, all of config 5) when ALL of these hold:
+ *   - num_graphs x epochs >= 20,000 walks, whether the kernel was chosen or pinned (fewer pairs than that do not fill regions),
+ *   - no GTOK_SENT_PACK_U8 (position ids reach 6 + 255 in its batches: 8-bit rows of such batches come from gtok_pack_rows_scan,
+ *     which raises status bit 0 where an id does not fit),
+ *   - ld <= 2040 at 16 bits / 1020 at 32 bits (a row's 16-byte pieces are counted in 8 bits).
+ * Everything else answers GTOK_E_UNSUPPORTED before anything is launched or written: call gtok_sent + gtok_pack_rows_scan.   */
 #define GTOK_SENT_PACK_ONLY 4 /* gtok_sent_params.flags, gtok_sent_packed only: the caller reads the PACKED rows alone - out_ids is then staging
                                 space of gtok_sent_pack_scratch_rows() rows x ld ids (contents unspecified afterwards) instead of a
                                 [K, G, ld] slab: every resident wave reuses its 64 rows for all of its units, the row stores stay in
