@@ -7,19 +7,21 @@
 // DESIGN.md §SENT (upstream AutoGraph parity is unpinned); the
 // bit-exact checker is oracle/gtok_oracle.c:oracle_sent.
 //
-// Three kernels, one spec:
-//   sent_lane_kernel (gtok_sent_lane.hpp) LANE per graph (64 graphs per wave): big batches of graphs with
-//                                         <= 64 nodes and <= 255 entries (every ZINC molecule)
-//   sent_reg_kernel  (gtok_sent_reg.hpp)  WAVE per graph, <= 64 nodes, adjacency rows in registers (lane = node)
-//   sent_lds_kernel  (gtok_sent_lds.hpp)  WAVE per graph, up to 512 nodes, immutable adjacency bit matrix in LDS
-// This file is the launcher: LDS layout, kernel choice, grid sizing.
+// Four kernels, one spec:
+//   sent_lane_kernel  (gtok_sent_lane.hpp)  LANE per graph (64 graphs per wave): big batches of graphs with
+//                                           <= 64 nodes and <= 255 entries (every ZINC molecule)
+//   sent_blane_kernel (gtok_sent_blane.hpp) LANE per graph over the adjacency bit-matrix mirror: big unlabelled batches, <= 256 nodes
+//   sent_reg_kernel   (gtok_sent_reg.hpp)   WAVE per graph, <= 64 nodes, adjacency rows in registers (lane = node)
+//   sent_lds_kernel   (gtok_sent_lds.hpp)   WAVE per graph, up to 512 nodes, immutable adjacency bit matrix in LDS
+// This file is the launcher: argument checks, kernel choice, and per kernel the LDS layout, instantiation and grid sizing.
+#include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 
 #include "gtok_common.hpp"
 #include "gtok.h"
 #include "gtok_sent_reg.hpp"
 #include "gtok_sent_lds.hpp"
-#include <cstdio>
 #include "gtok_sent_lane.hpp"
 #include "gtok_sent_blane.hpp"
 
@@ -28,48 +30,45 @@ namespace gtok {
 // below this many graphs a launch cannot fill the chip with 64-graph waves: wave-per-graph is used instead
 constexpr int GTOK_LANE_MIN_GRAPHS = 28000;     // measured crossover on ZINC-shaped molecules (lane 0.066 ms flat, reg 0.0025 ms per 1000 graphs)
 
-static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
-
-
 // below this many graphs the wave-per-graph LDS kernel is faster: the lane kernel's time is its longest walk (0.37 ms from
 // 4 k to 16 k graphs of 10-256 nodes, profiles/tools/blane_crossover.sh: ER crosses at ~24 k, the family mix at ~11 k)
 constexpr int GTOK_BLANE_MIN_GRAPHS = 20000;
 
-// 0 = lane-per-graph, 1 = register-resident wave-per-graph, 2 = LDS bit matrix, 3 = lane-per-graph over the adjacency
-// bit-matrix mirror.  GTOK_SENT_KERNEL=lane|reg|lds|blane pins a kernel where it is applicable (tests run every path).
+static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 static inline int sent_epochs(const gtok_sent_params *p) { return p->epoch_count > 1 ? p->epoch_count : 1; }
-static inline int ncu_hint() {     // compute units of the current device (256 on MI355X)
-  int dev = 0, ncu = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  return ncu > 0 ? ncu : 256;
-}
+static inline int sent_maxn(const gtok_csr *g) { return g->max_nodes > 0 ? g->max_nodes : 1; }
+// 64-bit words of an adjacency row (sent_lds_kernel's W; the mirror of sent_blane_kernel stops at 4)
+static inline int sent_words(int maxn) { return maxn <= 64 ? 1 : maxn <= 128 ? 2 : maxn <= 256 ? 4 : 8; }
 
-static int choose_sent_kernel(const gtok_csr *g, const gtok_sent_params *p) {
-  const int maxn = g->max_nodes > 0 ? g->max_nodes : 1;
+// Lane = lane-per-graph, Reg = register-resident wave-per-graph, Lds = LDS bit matrix, BLane = lane-per-graph over the adjacency
+// bit-matrix mirror; None: nothing to launch.  GTOK_SENT_KERNEL=lane|reg|lds|blane pins a kernel where it is applicable (tests run every path).
+enum class SentKernel { None, Lane, Reg, Lds, BLane };
+
+static SentKernel choose_sent_kernel(const gtok_csr *g, const gtok_sent_params *p) {
+  const int maxn = sent_maxn(g);
   // the lane-per-graph kernels need enough WALKS to fill the chip: K epochs of a small split count like one epoch of a big one
   const int64_t walks = (int64_t)g->num_graphs * sent_epochs(p);
   const char *pin = std::getenv("GTOK_SENT_KERNEL");
   const bool pin_lane = pin && pin[0] == 'l' && pin[1] == 'a', pin_reg = pin && pin[0] == 'r';
   const bool pin_lds = pin && pin[0] == 'l' && pin[1] == 'd', pin_blane = pin && pin[0] == 'b';
-  const int wneed = maxn <= 64 ? 1 : maxn <= 128 ? 2 : 4;
-  const bool blane_ok = !p->labeled && !p->remap_zinc && maxn <= 256 && g->adj_rows && g->adj_planes && g->adj_words == wneed &&
-                        g->adj_max_degree <= 255;
-  if (pin_blane && blane_ok) return 3;
+  const bool blane_ok = !p->labeled && !p->remap_zinc && maxn <= 256 && g->adj_rows && g->adj_planes &&
+                        g->adj_words == sent_words(maxn) && g->adj_max_degree <= 255;
+  if (pin_blane && blane_ok) return SentKernel::BLane;
   const bool fold_ok = !p->remap_zinc || g->max_nodes <= p->max_num_nodes;   // remap folded into constants
-  if (g->graph_ids || g->unit_ptr) {   // a reordered batch: the lane kernel or nothing (-1)
+  if (g->graph_ids || g->unit_ptr) {   // a reordered batch: the lane kernel or nothing
     const bool ok = g->graph_ids && g->unit_ptr && g->num_units > 0 && maxn <= 64 && g->max_edges <= 255 &&
                     (g->flags & GTOK_CSR_SIMPLE_SYMMETRIC) && fold_ok && g->chunk_nodes > 0;
-    return ok ? 0 : -1;
+    return ok ? SentKernel::Lane : SentKernel::None;
   }
   const bool lane_ok = maxn <= 64 && g->max_edges <= 255 && (g->flags & GTOK_CSR_SIMPLE_SYMMETRIC) && fold_ok;
   const bool reg_ok = maxn <= 64 && g->max_edges <= 32768 && fold_ok &&
                       22 + GTOK_SENT_IDX_OFFSET + p->max_num_nodes + p->num_node_types + 256 < kEdgeRef;
-  if (pin_lds) return 2;
-  if (pin_lane && lane_ok) return 0;
-  if (pin_reg && reg_ok) return 1;
-  if (lane_ok && !pin_reg && walks >= GTOK_LANE_MIN_GRAPHS) return 0;
-  if (blane_ok && !pin_reg && !pin_lane && walks >= GTOK_BLANE_MIN_GRAPHS) return 3;
-  return reg_ok ? 1 : 2;
+  if (pin_lds) return SentKernel::Lds;
+  if (pin_lane && lane_ok) return SentKernel::Lane;
+  if (pin_reg && reg_ok) return SentKernel::Reg;
+  if (lane_ok && !pin_reg && walks >= GTOK_LANE_MIN_GRAPHS) return SentKernel::Lane;
+  if (blane_ok && !pin_reg && !pin_lane && walks >= GTOK_BLANE_MIN_GRAPHS) return SentKernel::BLane;
+  return reg_ok ? SentKernel::Reg : SentKernel::Lds;
 }
 
 }  // namespace gtok
@@ -77,245 +76,262 @@ static int choose_sent_kernel(const gtok_csr *g, const gtok_sent_params *p) {
 using namespace gtok;
 
 namespace {
-struct PackDest { void *packed; int64_t capacity; int64_t *row_start; int64_t *state; };   // gtok_sent_packed
-}
 
-static int sent_impl(const gtok_csr *g, const gtok_sent_params *p, int32_t *out_ids, int32_t ld, int32_t *out_len,
-                     const PackDest *pd, void *stream) {
-  gtok::DeviceScope device_scope((hipStream_t)stream);   // the stream's device, not the thread's current one
-  if (!device_scope.ok()) return GTOK_E_NO_DEVICE;
+struct PackDest { void *packed; int64_t capacity; int64_t *row_start; int64_t *state; };   // gtok_sent_packed
+
+// one gtok_sent / gtok_sent_packed call: its arguments, and what check_sent_args derives from them for the launchers
+struct SentCall {
+  const gtok_csr *g; const gtok_sent_params *p; int32_t *out; int32_t ld; int32_t *out_len;
+  const PackDest *pd;      // gtok_sent_packed: where the walk packs its rows; else null
+  hipStream_t stream; int dev;   // (the stream's device: DeviceScope)
+  SentKernel which;
+  int K, maxn, maxe;       // epochs per launch, largest graph (>= 1 each)
+  bool u16, pk8;           // GTOK_SENT_U16, GTOK_SENT_PACK_U8
+  int pad_nt;              // pad with non-temporal stores (the lane-per-graph kernels)
+};
+
+// f(std::true_type) or f(std::false_type): a runtime flag as a template argument
+template <class F> auto with_flag(bool b, F f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+
+// Every test gtok_sent makes before a launcher fills its argument struct, in the order that decides which error an input
+// with two faults gets; fills the derived fields of `c` (which == None behind GTOK_OK: an empty batch, nothing to launch).
+int check_sent_args(SentCall &c) {
+  const gtok_csr *g = c.g; const gtok_sent_params *p = c.p; const PackDest *pd = c.pd; const int32_t ld = c.ld;
   if (!g || !p || ld <= 0 || g->num_graphs < 0) return GTOK_E_INVAL;
   if (g->num_graphs == 0) return GTOK_OK;   // an empty batch is a no-op
-  if (!out_ids || !out_len) return GTOK_E_INVAL;
+  if (!c.out || !c.out_len) return GTOK_E_INVAL;
   if (!g->node_ptr || !g->edge_ptr || !g->rowptr || (g->max_edges > 0 && !g->col)) return GTOK_E_INVAL;
   if (p->max_len < 0 || p->max_num_nodes < 0 || p->epoch_count < 0 || p->reserved != 0) return GTOK_E_INVAL;
   if (p->flags & ~(GTOK_SENT_NO_PAD | GTOK_SENT_U16 | (pd ? GTOK_SENT_PACK_ONLY | GTOK_SENT_PACK_U8 : 0))) return GTOK_E_INVAL;
-  const bool u16 = (p->flags & GTOK_SENT_U16) != 0;
-  const bool pk8 = (p->flags & GTOK_SENT_PACK_U8) != 0;      // one byte per id in the packed buffer; the slab / staging rows stay 16-bit
+  const bool u16 = c.u16 = (p->flags & GTOK_SENT_U16) != 0;
+  const bool pk8 = c.pk8 = (p->flags & GTOK_SENT_PACK_U8) != 0;      // one byte per id in the packed buffer; the slab / staging rows stay 16-bit
   if (pk8 && !u16) return GTOK_E_INVAL;
   if (u16 && (p->pad_id < 0 || p->pad_id > 65535)) return GTOK_E_INVAL;   // (the id space itself is checked below: tokens are 16 bits inside the kernels anyway)
-  const int K = sent_epochs(p);
+  const int K = c.K = sent_epochs(p);
   if ((int64_t)g->num_graphs * K > 0x7FFFFFFF / 2) return GTOK_E_TOO_LARGE;   // rows of the [K, G, ld] slab are counted in 32 bits
   if (p->labeled && (!g->nattr || !g->eattr)) return GTOK_E_INVAL;
   if (g->unit_info && !g->unit_ptr) return GTOK_E_INVAL;     // the per-unit records describe the units of unit_ptr
   if (g->max_nodes > GTOK_MAX_NODES) return GTOK_E_TOO_LARGE;
   if (g->max_edges > 60000) return GTOK_E_TOO_LARGE;   // neighbour lists are staged as uint16 in LDS
-  // tokens are staged as uint16
-  if ((int64_t)GTOK_SENT_IDX_OFFSET + p->max_num_nodes + p->num_node_types + 512 > 65535) return GTOK_E_TOO_LARGE;
+  if ((int64_t)GTOK_SENT_IDX_OFFSET + p->max_num_nodes + p->num_node_types + 512 > 65535) return GTOK_E_TOO_LARGE;   // tokens are staged as uint16
   if (g->max_nodes + GTOK_SENT_IDX_OFFSET > 65535) return GTOK_E_TOO_LARGE;
 
-  const int maxn = g->max_nodes > 0 ? g->max_nodes : 1;
-  const int W = maxn <= 64 ? 1 : maxn <= 128 ? 2 : maxn <= 256 ? 4 : 8;
-  const int cap = p->max_len < ld ? p->max_len : ld;
-  const int maxe = g->max_edges > 0 ? g->max_edges : 1;
-  const int which = choose_sent_kernel(g, p);
-  if (which < 0) return GTOK_E_INVAL;       // a reordered batch the lane-per-graph kernel cannot take
+  c.maxn = sent_maxn(g);
+  c.maxe = g->max_edges > 0 ? g->max_edges : 1;
+  const SentKernel which = c.which = choose_sent_kernel(g, p);
+  if (which == SentKernel::None) return GTOK_E_INVAL;       // a reordered batch the lane-per-graph kernel cannot take
   if (pd) {   // rows appended to a packed buffer by the walk itself: the two lane-per-graph kernels, rows that start on 16-byte boundaries
-    if (which != 0 && which != 3) return GTOK_E_UNSUPPORTED;
-    if (which == 3) {
+    const bool too_wide = ld > (u16 ? 2040 : 1020);         // (a row's 16-byte pieces are counted in 8 bits)
+    if (which != SentKernel::Lane && which != SentKernel::BLane) return GTOK_E_UNSUPPORTED;
+    if (which == SentKernel::BLane) {
       // the bit-matrix kernel packs where regions mean something (>= GTOK_BLANE_MIN_GRAPHS walks, chosen or pinned), at the slab's id
       // width (position ids reach 6 + 255 in its batches: no 8-bit rows) and with a row's pieces counted in 8 bits; everything
       // else keeps the two-call route (gtok_sent + gtok_pack_rows_scan), which callers take on this code
-      if ((int64_t)g->num_graphs * K < GTOK_BLANE_MIN_GRAPHS || pk8 || ld > (u16 ? 2040 : 1020)) return GTOK_E_UNSUPPORTED;
+      if ((int64_t)g->num_graphs * K < GTOK_BLANE_MIN_GRAPHS || pk8 || too_wide) return GTOK_E_UNSUPPORTED;
     }
     if (!pd->packed || !pd->row_start || !pd->state || pd->capacity < 0) return GTOK_E_INVAL;
-    if (ld > (u16 ? 2040 : 1020)) return GTOK_E_TOO_LARGE;    // (a row's 16-byte pieces are counted in 8 bits)
-    if (ld % (pk8 ? 16 : u16 ? 8 : 4) != 0 || (reinterpret_cast<uintptr_t>(out_ids) & 15u) || (reinterpret_cast<uintptr_t>(pd->packed) & 15u)) return GTOK_E_INVAL;
+    if (too_wide) return GTOK_E_TOO_LARGE;
+    if (ld % (pk8 ? 16 : u16 ? 8 : 4) != 0 || (reinterpret_cast<uintptr_t>(c.out) & 15u) || (reinterpret_cast<uintptr_t>(pd->packed) & 15u)) return GTOK_E_INVAL;
   }
   // padding with non-temporal stores once the slab outgrows the memory-side cache (256 MB on MI355X): gtok_sent_lane.hpp
-  int pad_nt = (int64_t)g->num_graphs * K * ld * (u16 ? 2 : 4) > ((int64_t)256 << 20);
-  if (const char *cs = std::getenv("GTOK_PAD_NT")) pad_nt = cs[0] != '0';   // tuning knob
-  const bool lane_path = which == 0, reg_path = which == 1;
-  if (which == 3) {
-    SentBLaneArgs a;
-    a.g = *g; a.p = *p; a.out = out_ids; a.ld = ld; a.out_len = out_len;
-    a.units = (g->num_graphs + 63) / 64;
-    a.epochs = K;
-    a.pad_nt = pad_nt;
-    a.prio = 1;
-    a.pack_out = pd ? pd->packed : nullptr;
-    a.pack_start = pd ? pd->row_start : nullptr;
-    a.pack_state = pd ? reinterpret_cast<unsigned long long *>(pd->state) : nullptr;
-    a.pack_region_cap = 0; a.pack_regions = 1;
-    a.pack_scratch = pd && (p->flags & GTOK_SENT_PACK_ONLY) ? 1 : 0;
-    if (a.pack_scratch) a.p.flags |= GTOK_SENT_NO_PAD;                   // (nobody reads the staging rows' tails)
-    if (const char *cs = std::getenv("GTOK_BLANE_PRIO")) a.prio = cs[0] != '0';   // tuning knob
-    const bool p4 = g->adj_max_degree <= 15;
-    typedef void (*KF)(const SentBLaneArgs);
-#define GTOK_BLANE_K(U)                                                                                 \
-  (W == 1 ? (p4 ? (KF)sent_blane_kernel<1, 4, U> : (KF)sent_blane_kernel<1, 8, U>)                     \
-   : W == 2 ? (p4 ? (KF)sent_blane_kernel<2, 4, U> : (KF)sent_blane_kernel<2, 8, U>)                   \
-            : (p4 ? (KF)sent_blane_kernel<4, 4, U> : (KF)sent_blane_kernel<4, 8, U>))
-    KF kern = u16 ? GTOK_BLANE_K(true) : GTOK_BLANE_K(false);
-#undef GTOK_BLANE_K
-    if (pd) {   // gtok_sent_packed: the instantiations that append to the packed buffer
-#define GTOK_BLANE_KP(U)                                                                                            \
-  (W == 1 ? (p4 ? (KF)sent_blane_kernel<1, 4, U, true> : (KF)sent_blane_kernel<1, 8, U, true>)                     \
-   : W == 2 ? (p4 ? (KF)sent_blane_kernel<2, 4, U, true> : (KF)sent_blane_kernel<2, 8, U, true>)                   \
-            : (p4 ? (KF)sent_blane_kernel<4, 4, U, true> : (KF)sent_blane_kernel<4, 8, U, true>))
-      kern = u16 ? GTOK_BLANE_KP(true) : GTOK_BLANE_KP(false);
-#undef GTOK_BLANE_KP
-    }
-    const size_t lds = (size_t)5120 * W;   // 20 W dwords per lane (gtok_sent_blane.hpp)
-    const int dev = device_scope.dev, ncu = device_cu_count(dev);
-    // one workgroup per CU: 8 waves at W = 4 (160 KB of LDS, 2 per SIMD: the register file holds no more), else 16
-    int nw = W == 4 ? 8 : 16;
-    if (const char *cs = std::getenv("GTOK_BLANE_WAVES")) { const int c = std::atoi(cs); if (c == 4 || c == 8 || c == 16) nw = c < nw ? c : nw; }   // tuning knob
-    if (!raise_lds_limit(reinterpret_cast<const void *>(kern), dev)) return GTOK_E_LAUNCH;
-    const int vun = a.units * K;
-    const int nb = vun < ncu ? vun : ncu;   // every CU, also when some of its waves stay without a unit
-    if (pd) {   // regions of the packed buffer: the molecule kernel's rule (pairs are dealt unit-major and lane_order stores the units by
-                // expected length, so vu mod regions hands every region the same mix); staging: 64 rows x nw <= 16 waves x nb <= CUs
-      int m = GTOK_PACK_REGIONS;
-      while (m > 1 && vun < 64 * m) m >>= 1;
-      a.pack_regions = m;
-      a.pack_region_cap = (pd->capacity / m) & ~(int64_t)7;
-    }
-    if (2 * nb > kSlotInts) return GTOK_E_TOO_LARGE;      // (two ticket words per workgroup in one counter block: 528 CUs)
-    // unit-major always: the K walks of a unit fetch the same adjacency rows at about the same time (L2 hits on the one HBM read
-    // of a step) - 125 k ER graphs x 8 epochs: 0.356 ms per epoch against 0.404 epoch-major (0.49 for one epoch per launch)
-    a.epoch_major = 0;
-    if (const char *cs = std::getenv("GTOK_LANE_PAIR_ORDER")) a.epoch_major = cs[0] == 'e';   // tuning knob: unit | epoch
-    // the ticket counters of the pairs beyond the first round: a block of this launch's own, in device memory, zero between launches
-    QueueSlot slot = take_queue_slot(dev, (hipStream_t)stream);
-    if (!slot.counters) return slot.graph_pool_empty ? GTOK_E_GRAPH_SLOTS : GTOK_E_LAUNCH;
-    a.tickets = slot.counters;
-    hipLaunchKernelGGL(kern, dim3(nb), dim3(64 * nw), lds * nw, (hipStream_t)stream, a);
-    mark_queue_slot(slot, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? GTOK_OK : GTOK_E_LAUNCH;
+  c.pad_nt = (int64_t)g->num_graphs * K * ld * (u16 ? 2 : 4) > ((int64_t)256 << 20);
+  if (const char *cs = std::getenv("GTOK_PAD_NT")) c.pad_nt = cs[0] != '0';   // tuning knob
+  return GTOK_OK;
+}
+
+// The gtok_sent_packed part of SentLaneArgs / SentBLaneArgs: the destination, and the regions of the packed buffer - as many as leave
+// every region >= 64 of the launch's `vunits` (unit, epoch) pairs.  They fill evenly: the molecule kernel deals its pairs by rank in walk
+// length; the bit-matrix kernel deals them unit-major and lane_order stores the units by expected length (vu mod regions: the same mix).
+template <class Args> void plan_pack(Args &a, const PackDest *pd, int vunits) {
+  a.pack_out = pd ? pd->packed : nullptr;
+  a.pack_start = pd ? pd->row_start : nullptr;
+  a.pack_state = pd ? reinterpret_cast<unsigned long long *>(pd->state) : nullptr;
+  a.pack_region_cap = 0; a.pack_regions = 1; a.pack_scratch = pd && (a.p.flags & GTOK_SENT_PACK_ONLY) ? 1 : 0;
+  if (!pd) return;
+  if (a.pack_scratch) a.p.flags |= GTOK_SENT_NO_PAD;                   // (nobody reads the staging rows' tails)
+  int m = GTOK_PACK_REGIONS;
+  while (m > 1 && vunits < 64 * m) m >>= 1;
+  a.pack_regions = m;
+  // a region holds whole 16-byte pieces: 8 ids, 16 of one byte (GTOK_SENT_PACK_U8: the molecule kernel only)
+  a.pack_region_cap = (pd->capacity / m) & ~(int64_t)((a.p.flags & GTOK_SENT_PACK_U8) ? 15 : 7);
+}
+
+// ---- sent_blane_kernel: one workgroup per CU, (unit, epoch) pairs drawn from per-workgroup tickets
+typedef void (*BLaneKernel)(const SentBLaneArgs);
+
+template <int W> BLaneKernel blane_kernel(bool p4, bool u16, bool pack) {   // pack: the instantiations that append to the packed buffer
+  return with_flag(p4, [=](auto p4_) {
+    return with_flag(u16, [=](auto u16_) {
+      return with_flag(pack, [](auto pack_) -> BLaneKernel {
+        return sent_blane_kernel<W, decltype(p4_)::value ? 4 : 8, decltype(u16_)::value, decltype(pack_)::value>;
+      });
+    });
+  });
+}
+
+int launch_blane(const SentCall &c) {
+  const gtok_csr *g = c.g; const int K = c.K, W = sent_words(c.maxn);
+  SentBLaneArgs a;
+  a.g = *g; a.p = *c.p; a.out = c.out; a.ld = c.ld; a.out_len = c.out_len;
+  a.units = (g->num_graphs + 63) / 64; a.epochs = K; a.pad_nt = c.pad_nt; a.prio = 1;
+  if (const char *cs = std::getenv("GTOK_BLANE_PRIO")) a.prio = cs[0] != '0';   // tuning knob
+  const bool p4 = g->adj_max_degree <= 15, pack = c.pd != nullptr;
+  const BLaneKernel kern = W == 1 ? blane_kernel<1>(p4, c.u16, pack) : W == 2 ? blane_kernel<2>(p4, c.u16, pack) : blane_kernel<4>(p4, c.u16, pack);
+  const size_t lds = (size_t)5120 * W;   // 20 W dwords per lane (gtok_sent_blane.hpp)
+  const int ncu = device_cu_count(c.dev);
+  // one workgroup per CU: 8 waves at W = 4 (160 KB of LDS, 2 per SIMD: the register file holds no more), else 16
+  int nw = W == 4 ? 8 : 16;
+  if (const char *cs = std::getenv("GTOK_BLANE_WAVES")) { const int n = std::atoi(cs); if (n == 4 || n == 8 || n == 16) nw = n < nw ? n : nw; }   // tuning knob
+  if (!raise_lds_limit(reinterpret_cast<const void *>(kern), c.dev)) return GTOK_E_LAUNCH;
+  const int vun = a.units * K;
+  const int nb = vun < ncu ? vun : ncu;   // every CU, also when some of its waves stay without a unit
+  plan_pack(a, c.pd, vun);                // (staging: 64 rows x nw <= 16 waves x nb <= CUs)
+  if (2 * nb > kSlotInts) return GTOK_E_TOO_LARGE;      // (two ticket words per workgroup in one counter block: 528 CUs)
+  // unit-major always: the K walks of a unit fetch the same adjacency rows at about the same time (L2 hits on the one HBM read
+  // of a step) - 125 k ER graphs x 8 epochs: 0.356 ms per epoch against 0.404 epoch-major (0.49 for one epoch per launch)
+  a.epoch_major = 0;
+  if (const char *cs = std::getenv("GTOK_LANE_PAIR_ORDER")) a.epoch_major = cs[0] == 'e';   // tuning knob: unit | epoch
+  // the ticket counters of the pairs beyond the first round: a block of this launch's own, in device memory, zero between launches
+  QueueSlot slot = take_queue_slot(c.dev, c.stream);
+  if (!slot.counters) return slot.graph_pool_empty ? GTOK_E_GRAPH_SLOTS : GTOK_E_LAUNCH;
+  a.tickets = slot.counters;
+  hipLaunchKernelGGL(kern, dim3(nb), dim3(64 * nw), lds * nw, c.stream, a);
+  mark_queue_slot(slot, c.stream);
+  return hipGetLastError() == hipSuccess ? GTOK_OK : GTOK_E_LAUNCH;
+}
+
+// ---- sent_lane_kernel: a 64-graph unit staged in a wave's slice of LDS
+typedef void (*LaneKernel)(const SentLaneArgs);
+
+// MODE: 0 unlabelled, 1 labelled, 2 labelled with the ZINC remap folded in (an unlabelled row has nothing to remap)
+template <int MODE, int P, bool PK, bool U16, bool PACK, bool PK8>
+LaneKernel lane_instance() { return sent_lane_kernel<MODE != 0, P, MODE == 2, PK, U16, PACK, PK8>; }
+// p3: 4 counter planes, else 6; pk: the batch has its byte mirror; pack: the instantiations that append to the packed buffer (batches
+// with the byte mirror only), pk8: at one byte per id (16-bit rows only)
+template <int MODE> LaneKernel lane_kernel(bool p3, bool pk, bool u16, bool pack, bool pk8) {
+  return with_flag(p3, [=](auto p3_) -> LaneKernel {
+    constexpr int P = decltype(p3_)::value ? 4 : 6;
+    if (pk8) return lane_instance<MODE, P, true, true, true, true>();
+    return with_flag(u16, [=](auto u16_) -> LaneKernel {
+      constexpr bool U16 = decltype(u16_)::value;
+      if (pack) return lane_instance<MODE, P, true, U16, true, false>();
+      return pk ? lane_instance<MODE, P, true, U16, false, false>() : lane_instance<MODE, P, false, U16, false, false>();
+    });
+  });
+}
+
+// A reordered batch: one 16-wave workgroup per CU (the kernel pairs long units with short ones on every SIMD) when a
+// wave's share of the CU's 160 KB is enough and the batch fills the chip.  Returns whether it launched (*rc: the outcome);
+// else the caller launches one-wave workgroups with the units spread.
+bool launch_lane_per_cu(const SentCall &c, const SentLaneArgs &a, LaneKernel kern, int vunits, int ncu, int *rc) {
+  const char *wg = std::getenv("GTOK_LANE_PER_CU");   // tuning knob: 0 = never
+  // (+ kLaneWgShared bytes: the workgroup's ticket counter, from which its waves draw their units after the first round,
+  // and the words through which they share the padding of their last units)
+  if (!c.g->unit_ptr || a.lds * 16 + kLaneWgShared > 160 * 1024 || vunits < 4 * ncu || (wg && wg[0] == '0')) return false;
+  // (the opt-in to more than 64 KB of dynamic LDS is per kernel and per device: a host-side call of a microsecond)
+  const bool r = raise_lds_limit(reinterpret_cast<const void *>(kern), c.dev);
+  // One 16-wave workgroup per CU, except where ONE nearly full round of units ends in the int32 slab's padding (ZINC-full x 1
+  // epoch, a 31 k shard x 8): there two 8-wave workgroups per CU let one half of a CU pad while the other still walks
+  // (0.0740 against 0.0769 ms, 8.98 against 9.50 us per epoch; every other shape - fewer units, several rounds, 16-bit rows,
+  // no padding - is 1-4 % better with 16: profiles/r04/wg_waves.txt)
+  const int slots = ncu * 16;
+  const bool one_full_round = vunits <= slots && 4 * (int64_t)vunits > 3 * (int64_t)slots;
+  const char *ww = std::getenv("GTOK_LANE_WG_WAVES");   // tuning knob: 8 = two 8-wave workgroups per CU
+  const int wgw = ww ? ((ww[0] == '8') ? 8 : (ww[0] == '1' && ww[1] == '2') ? 12 : 16)   // 12: three waves per SIMD
+                     : (one_full_round && !c.u16 && !(c.p->flags & GTOK_SENT_NO_PAD) ? 8 : 16);
+  const int per_cu = wgw == 8 ? 2 : 1;
+  const size_t wg_lds = (size_t)a.lds * wgw + kLaneWgShared;
+  if (r && occupancy_of(reinterpret_cast<const void *>(kern), c.dev, 64 * wgw, wg_lds) >= per_cu) {
+    hipLaunchKernelGGL(kern, dim3(ncu * per_cu), dim3(64 * wgw), wg_lds, c.stream, a);
+    *rc = hipGetLastError() == hipSuccess ? GTOK_OK : GTOK_E_LAUNCH;
+    return true;
   }
-  if (lane_path) {
-    SentLaneArgs a;
-    a.g = *g; a.p = *p; a.maxn = maxn; a.out = out_ids; a.ld = ld; a.out_len = out_len;
-    a.pack_out = pd ? pd->packed : nullptr;
-    a.pack_start = pd ? pd->row_start : nullptr;
-    a.pack_state = pd ? reinterpret_cast<unsigned long long *>(pd->state) : nullptr;
-    a.pack_region_cap = 0; a.pack_regions = 1;
-    a.pack_scratch = pd && (p->flags & GTOK_SENT_PACK_ONLY) ? 1 : 0;
-    if (a.pack_scratch) a.p.flags |= GTOK_SENT_NO_PAD;                   // (nobody reads the staging rows' tails)
-    // staging sized by the largest 64-graph chunk when the host told us, else by the per-graph maxima
-    a.cap_n = g->chunk_nodes > 0 ? g->chunk_nodes : 64 * maxn;
-    a.cap_e = g->chunk_edges > 0 ? g->chunk_edges : 64 * maxe;
-    a.cap_r = a.cap_n + 64;
-    int off = 0;
-    a.off_rp = off; off += align_up(a.cap_r + 16, 16);  // + 16: the counter set-up reads whole dwords around a lane's row pointers
-    a.off_col = off; off += align_up(a.cap_e + 8, 16);   // +8: a row's first four entries are read as an aligned dword pair
-    a.off_eat = a.off_nat = off;
-    if (p->labeled) {
-      a.off_eat = off; off += align_up(a.cap_e + 8, 16);
-      a.off_nat = off; off += align_up(a.cap_n + 8, 16);
-    } else {
-      a.off_nat = off; off += align_up(a.cap_n + 8, 16);  // unlabelled: the node -> visit index table alone
-    }
-    a.lds = align_up(off, 16);
-    if (a.lds < 512) a.lds = 512;       // (a wave's slice also carries its last unit's 64 (row, pad start) pairs: the shared padding)
-    if (a.lds > 64 * 1024) return GTOK_E_TOO_LARGE;
-    // counter planes: degree < 2^P; an unknown max_degree is covered by P = 6 (a node of a simple graph with <= 64 nodes has < 64 neighbours)
-    const bool p3 = g->max_degree > 0 && g->max_degree <= 15;
-    typedef void (*KF)(const SentLaneArgs);
-    const bool pk = g->rowptr8 && g->col8;
-#define GTOK_LANE_K2(LAB, REMAP, U)                                                                                   \
-  (pk ? (p3 ? (KF)sent_lane_kernel<LAB, 4, REMAP, true, U> : (KF)sent_lane_kernel<LAB, 6, REMAP, true, U>)            \
-      : (p3 ? (KF)sent_lane_kernel<LAB, 4, REMAP, false, U> : (KF)sent_lane_kernel<LAB, 6, REMAP, false, U>))
-#define GTOK_LANE_K(LAB, REMAP) (u16 ? GTOK_LANE_K2(LAB, REMAP, true) : GTOK_LANE_K2(LAB, REMAP, false))
-    KF kern = !p->labeled ? GTOK_LANE_K(false, false) : p->remap_zinc ? GTOK_LANE_K(true, true) : GTOK_LANE_K(true, false);
-#undef GTOK_LANE_K
-#undef GTOK_LANE_K2
-    if (pd) {   // gtok_sent_packed: the instantiations that append to the packed buffer (batches with the byte mirror only)
-      if (!pk) return GTOK_E_UNSUPPORTED;
-#define GTOK_LANE_KP2(LAB, REMAP, U) (p3 ? (KF)sent_lane_kernel<LAB, 4, REMAP, true, U, true> : (KF)sent_lane_kernel<LAB, 6, REMAP, true, U, true>)
-#define GTOK_LANE_KP(LAB, REMAP) (u16 ? GTOK_LANE_KP2(LAB, REMAP, true) : GTOK_LANE_KP2(LAB, REMAP, false))
-      kern = !p->labeled ? GTOK_LANE_KP(false, false) : p->remap_zinc ? GTOK_LANE_KP(true, true) : GTOK_LANE_KP(true, false);
-#undef GTOK_LANE_KP
-#undef GTOK_LANE_KP2
-      if (pk8) {
-#define GTOK_LANE_KP8(LAB, REMAP) (p3 ? (KF)sent_lane_kernel<LAB, 4, REMAP, true, true, true, true> : (KF)sent_lane_kernel<LAB, 6, REMAP, true, true, true, true>)
-        kern = !p->labeled ? GTOK_LANE_KP8(false, false) : p->remap_zinc ? GTOK_LANE_KP8(true, true) : GTOK_LANE_KP8(true, false);
-#undef GTOK_LANE_KP8
-      }
-    }
-    const int dev = device_scope.dev, ncu = device_cu_count(dev);
-    int occ = -1;                                 // occupancy of one-wave workgroups: only the fallback launch below asks
-    if (const char *cs = std::getenv("GTOK_LANE_BLOCKS_PER_CU")) {   // tuning knob
-      occ = occupancy_of(reinterpret_cast<const void *>(kern), dev, 64, (size_t)a.lds);
-      if (occ < 1) occ = 1;
-      const int c = std::atoi(cs);
-      if (c >= 1 && c < occ) occ = c;
-    }
-    a.units = g->unit_ptr ? g->num_units : (g->num_graphs + 63) / 64;
-    a.epochs = K;
-    a.pad_nt = pad_nt;
-    a.epoch_major = 0;     // set below, once the launch shape is known
-    if ((int64_t)a.units * K > 0x7FFFFFFF / 64) return GTOK_E_TOO_LARGE;
-    const int vunits = a.units * K;               // (unit, epoch) pairs the launch walks
-    if (pd) {   // regions of the packed buffer: as many as leave every region >= 64 pairs (they fill evenly: pairs are dealt by rank in walk length)
-      int m = GTOK_PACK_REGIONS;
-      while (m > 1 && vunits < 64 * m) m >>= 1;
-      a.pack_regions = m;
-      a.pack_region_cap = (pd->capacity / m) & ~(int64_t)(pk8 ? 15 : 7);
-    }
-    // order of the pairs: unit-major (the K walks of a unit side by side: the deal stays sorted by walk length) for splits that
-    // need several epochs to fill the chip; epoch-major (epoch 0 of every unit, then epoch 1, ...) when one epoch fills half of
-    // the resident waves or more - the first round is then the tuned one-epoch deal (249,456 molecules x 2 epochs, int32 padded:
-    // 0.076 ms per epoch against 0.089; x 4 as 16-bit rows: 0.0573 against 0.0589; 12 k x 24: 0.0043 against 0.0039 the other way)
-    a.epoch_major = K > 1 && a.units >= 8 * ncu;
-    if (const char *cs = std::getenv("GTOK_LANE_PAIR_ORDER")) a.epoch_major = cs[0] == 'e';   // tuning knob: unit | epoch
-    a.unit_mul = 0;
-    a.prio_cut[0] = 16; a.prio_cut[1] = 32; a.prio_cut[2] = 48;   // quartiles (profiles/tools/lane_prio_sweep.sh)
-    if (const char *pc = std::getenv("GTOK_LANE_PRIO_CUTS")) std::sscanf(pc, "%d,%d,%d", &a.prio_cut[0], &a.prio_cut[1], &a.prio_cut[2]);   // tuning knob
-    // a reordered batch: one 16-wave workgroup per CU (the kernel pairs long units with short ones on every SIMD) when a
-    // wave's share of the CU's 160 KB is enough and the batch fills the chip; else one-wave workgroups with the units spread
-    const char *wg = std::getenv("GTOK_LANE_PER_CU");   // tuning knob: 0 = never
-    // (+ kLaneWgShared bytes: the workgroup's ticket counter, from which its waves draw their units after the first round,
-    // and the words through which they share the padding of their last units)
-    if (g->unit_ptr && a.lds * 16 + kLaneWgShared <= 160 * 1024 && vunits >= 4 * ncu && !(wg && wg[0] == '0')) {
-      // (the opt-in to more than 64 KB of dynamic LDS is per kernel and per device: a host-side call of a microsecond)
-      const bool r = raise_lds_limit(reinterpret_cast<const void *>(kern), dev);
-      int occ16 = 0;
-      // One 16-wave workgroup per CU, except where ONE nearly full round of units ends in the int32 slab's padding (ZINC-full x 1
-      // epoch, a 31 k shard x 8): there two 8-wave workgroups per CU let one half of a CU pad while the other still walks
-      // (0.0740 against 0.0769 ms, 8.98 against 9.50 us per epoch; every other shape - fewer units, several rounds, 16-bit rows,
-      // no padding - is 1-4 % better with 16: profiles/r04/wg_waves.txt)
-      const int slots = ncu * 16;
-      const bool one_full_round = vunits <= slots && 4 * (int64_t)vunits > 3 * (int64_t)slots;
-      const char *ww = std::getenv("GTOK_LANE_WG_WAVES");   // tuning knob: 8 = two 8-wave workgroups per CU
-      const int wgw = ww ? ((ww[0] == '8') ? 8 : (ww[0] == '1' && ww[1] == '2') ? 12 : 16)   // 12: three waves per SIMD
-                         : (one_full_round && !u16 && !(p->flags & GTOK_SENT_NO_PAD) ? 8 : 16);
-      const int per_cu = wgw == 8 ? 2 : 1;
-      const size_t wg_lds = (size_t)a.lds * wgw + kLaneWgShared;
-      if (r && (occ16 = occupancy_of(reinterpret_cast<const void *>(kern), dev, 64 * wgw, wg_lds)) >= per_cu) {
-        hipLaunchKernelGGL(kern, dim3(ncu * per_cu), dim3(64 * wgw), wg_lds, (hipStream_t)stream, a);
-        return hipGetLastError() == hipSuccess ? GTOK_OK : GTOK_E_LAUNCH;
-      }
-      (void)hipGetLastError();
-    }
-    if (g->unit_ptr && vunits > 16) {
-      auto gcd = [](int x, int y) { while (y) { const int t = x % y; x = y; y = t; } return x; };
-      int m = (int)(vunits * 0.6180339887498949);
-      while (gcd(m, vunits) != 1) ++m;
-      a.unit_mul = m;
-    }
-    if (occ < 0) {
-      occ = occupancy_of(reinterpret_cast<const void *>(kern), dev, 64, (size_t)a.lds);
-      if (occ < 1) occ = 1;
-    }
-    int nb = ncu * occ;
-    if (nb > vunits) nb = vunits;
-    if (a.pack_scratch && nb > ncu * 16) nb = ncu * 16;     // (the staging space is 64 rows for each of 16 waves per CU)
-    hipLaunchKernelGGL(kern, dim3(nb), dim3(64), (size_t)a.lds, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? GTOK_OK : GTOK_E_LAUNCH;
+  (void)hipGetLastError();
+  return false;
+}
+
+int launch_lane(const SentCall &c) {
+  const gtok_csr *g = c.g; const gtok_sent_params *p = c.p; const int K = c.K;
+  SentLaneArgs a;
+  a.g = *g; a.p = *p; a.maxn = c.maxn; a.out = c.out; a.ld = c.ld; a.out_len = c.out_len;
+  // the LDS slice of a wave - staging sized by the largest 64-graph chunk when the host told us, else by the per-graph maxima
+  a.cap_n = g->chunk_nodes > 0 ? g->chunk_nodes : 64 * c.maxn;
+  a.cap_e = g->chunk_edges > 0 ? g->chunk_edges : 64 * c.maxe;
+  a.cap_r = a.cap_n + 64;
+  int off = 0;
+  a.off_rp = off; off += align_up(a.cap_r + 16, 16);  // + 16: the counter set-up reads whole dwords around a lane's row pointers
+  a.off_col = off; off += align_up(a.cap_e + 8, 16);   // +8: a row's first four entries are read as an aligned dword pair
+  a.off_eat = off;
+  if (p->labeled) off += align_up(a.cap_e + 8, 16);
+  a.off_nat = off; off += align_up(a.cap_n + 8, 16);  // (unlabelled: the node -> visit index table alone, where the edge types would be)
+  a.lds = align_up(off, 16);
+  if (a.lds < 512) a.lds = 512;       // (a wave's slice also carries its last unit's 64 (row, pad start) pairs: the shared padding)
+  if (a.lds > 64 * 1024) return GTOK_E_TOO_LARGE;
+  // counter planes: degree < 2^P; an unknown max_degree is covered by P = 6 (a node of a simple graph with <= 64 nodes has < 64 neighbours)
+  const bool p3 = g->max_degree > 0 && g->max_degree <= 15;
+  const bool pk = g->rowptr8 && g->col8, pack = c.pd != nullptr;
+  if (pack && !pk) return GTOK_E_UNSUPPORTED;
+  const LaneKernel kern = !p->labeled ? lane_kernel<0>(p3, pk, c.u16, pack, c.pk8)
+                          : p->remap_zinc ? lane_kernel<2>(p3, pk, c.u16, pack, c.pk8) : lane_kernel<1>(p3, pk, c.u16, pack, c.pk8);
+  const int ncu = device_cu_count(c.dev);
+  int occ = -1;                                 // occupancy of one-wave workgroups: only the fallback launch below asks
+  if (const char *cs = std::getenv("GTOK_LANE_BLOCKS_PER_CU")) {   // tuning knob
+    occ = occupancy_of(reinterpret_cast<const void *>(kern), c.dev, 64, (size_t)a.lds);
+    if (occ < 1) occ = 1;
+    const int n = std::atoi(cs);
+    if (n >= 1 && n < occ) occ = n;
   }
+  a.units = g->unit_ptr ? g->num_units : (g->num_graphs + 63) / 64; a.epochs = K; a.pad_nt = c.pad_nt;
+  if ((int64_t)a.units * K > 0x7FFFFFFF / 64) return GTOK_E_TOO_LARGE;
+  const int vunits = a.units * K;               // (unit, epoch) pairs the launch walks
+  plan_pack(a, c.pd, vunits);
+  // order of the pairs: unit-major (the K walks of a unit side by side: the deal stays sorted by walk length) for splits that
+  // need several epochs to fill the chip; epoch-major (epoch 0 of every unit, then epoch 1, ...) when one epoch fills half of
+  // the resident waves or more - the first round is then the tuned one-epoch deal (249,456 molecules x 2 epochs, int32 padded:
+  // 0.076 ms per epoch against 0.089; x 4 as 16-bit rows: 0.0573 against 0.0589; 12 k x 24: 0.0043 against 0.0039 the other way)
+  a.epoch_major = K > 1 && a.units >= 8 * ncu;
+  if (const char *cs = std::getenv("GTOK_LANE_PAIR_ORDER")) a.epoch_major = cs[0] == 'e';   // tuning knob: unit | epoch
+  a.unit_mul = 0;
+  a.prio_cut[0] = 16; a.prio_cut[1] = 32; a.prio_cut[2] = 48;   // quartiles (profiles/tools/lane_prio_sweep.sh)
+  if (const char *pc = std::getenv("GTOK_LANE_PRIO_CUTS")) std::sscanf(pc, "%d,%d,%d", &a.prio_cut[0], &a.prio_cut[1], &a.prio_cut[2]);   // tuning knob
+  int rc;
+  if (launch_lane_per_cu(c, a, kern, vunits, ncu, &rc)) return rc;
+  if (g->unit_ptr && vunits > 16) {
+    auto gcd = [](int x, int y) { while (y) { const int t = x % y; x = y; y = t; } return x; };
+    int m = (int)(vunits * 0.6180339887498949);
+    while (gcd(m, vunits) != 1) ++m;
+    a.unit_mul = m;
+  }
+  if (occ < 0) {
+    occ = occupancy_of(reinterpret_cast<const void *>(kern), c.dev, 64, (size_t)a.lds);
+    if (occ < 1) occ = 1;
+  }
+  int nb = ncu * occ;
+  if (nb > vunits) nb = vunits;
+  if (a.pack_scratch && nb > ncu * 16) nb = ncu * 16;     // (the staging space is 64 rows for each of 16 waves per CU)
+  hipLaunchKernelGGL(kern, dim3(nb), dim3(64), (size_t)a.lds, c.stream, a);
+  return hipGetLastError() == hipSuccess ? GTOK_OK : GTOK_E_LAUNCH;
+}
+
+// ---- sent_reg_kernel / sent_lds_kernel: wave per graph
+typedef void (*WaveKernel)(const SentArgs);
+
+template <int W> WaveKernel lds_kernel(bool labeled) { return labeled ? (WaveKernel)sent_lds_kernel<W, true> : (WaveKernel)sent_lds_kernel<W, false>; }
+
+int launch_wave(const SentCall &c) {
+  const gtok_csr *g = c.g; const gtok_sent_params *p = c.p;
+  const bool reg_path = c.which == SentKernel::Reg;
+  const int K = c.K, maxn = c.maxn, maxe = c.maxe, W = sent_words(maxn);
   SentArgs a;
-  a.g = *g; a.p = *p; a.cap = cap; a.maxn = maxn; a.out = out_ids; a.ld = ld; a.out_len = out_len;
-  a.epochs = K;
+  a.g = *g; a.p = *p; a.cap = p->max_len < c.ld ? p->max_len : c.ld; a.maxn = maxn; a.out = c.out; a.ld = c.ld; a.out_len = c.out_len; a.epochs = K;
   const int pairs = g->num_graphs * K;          // (epoch, graph) pairs the launch walks
+  // no store of the walk is bounds-checked: room for the longest possible trail (or max_len) + one iteration
+  const int64_t bound = p->labeled ? 2 + 7 * (int64_t)maxn + 2 * (int64_t)maxe : 2 + 5 * (int64_t)maxn + (int64_t)maxe;
+  const int tokcap = (int)(bound < p->max_len ? bound : p->max_len) + kSentSlack + (reg_path ? 0 : 2 * maxn);
   int off = 0;
   if (reg_path) {
     a.l.adj = off; off += 64 * 8;
     a.l.vis = a.l.rng = a.l.vidx = a.l.order = a.l.nat = 0;
-    // no store of the walk is bounds-checked: room for the longest possible trail (or max_len) + one iteration
-    const int64_t bound = p->labeled ? 2 + 7 * (int64_t)maxn + 2 * (int64_t)maxe : 2 + 5 * (int64_t)maxn + (int64_t)maxe;
-    const int tokcap = (int)(bound < p->max_len ? bound : p->max_len) + kSentSlack;
     a.l.tok = off; off += align_up(tokcap * 2, 8);
     a.l.rp = a.l.eat = off;
     a.l.col = off; off += align_up(maxe * 2, 8);          // staged neighbour ids
@@ -324,8 +340,6 @@ static int sent_impl(const gtok_csr *g, const gtok_sent_params *p, int32_t *out_
       a.l.eat = off; off += align_up(maxe, 8);
     }
   } else {
-    const int64_t bound = p->labeled ? 2 + 7 * (int64_t)maxn + 2 * (int64_t)maxe : 2 + 5 * (int64_t)maxn + (int64_t)maxe;
-    const int tokcap = (int)(bound < p->max_len ? bound : p->max_len) + kSentSlack + 2 * maxn;
     a.l.adj = off; off += maxn * W * 8;
     a.l.vis = a.l.rng = a.l.vidx = 0;
     a.l.order = off; off += align_up(maxn * 2, 8);
@@ -345,37 +359,19 @@ static int sent_impl(const gtok_csr *g, const gtok_sent_params *p, int32_t *out_
   while (wpb > 1 && wpb * a.l.stride > 64 * 1024) wpb >>= 1;
   const size_t lds = (size_t)wpb * a.l.stride;
 
-  void (*kern)(const SentArgs) = nullptr;
-#define PICK(w)                                                                   \
-  kern = p->labeled ? (void (*)(const SentArgs))sent_lds_kernel<w, true>         \
-                    : (void (*)(const SentArgs))sent_lds_kernel<w, false>
+  WaveKernel kern;
   if (reg_path) {
     // no truncation test in the walk when max_len can hold the longest possible trail of this batch
-    const int64_t bound = p->labeled ? 2 + 7 * (int64_t)maxn + 2 * (int64_t)maxe : 2 + 5 * (int64_t)maxn + (int64_t)maxe;
     const bool nolim = bound <= p->max_len;
-    typedef void (*KF)(const SentArgs);
-    kern = p->labeled ? (nolim ? (KF)sent_reg_kernel<true, true> : (KF)sent_reg_kernel<true, false>)
-                      : (nolim ? (KF)sent_reg_kernel<false, true> : (KF)sent_reg_kernel<false, false>);
+    kern = p->labeled ? (nolim ? (WaveKernel)sent_reg_kernel<true, true> : (WaveKernel)sent_reg_kernel<true, false>)
+                      : (nolim ? (WaveKernel)sent_reg_kernel<false, true> : (WaveKernel)sent_reg_kernel<false, false>);
   } else {
-    switch (W) {
-      case 1: PICK(1); break;
-      case 2: PICK(2); break;
-      case 4: PICK(4); break;
-      default: PICK(8); break;
-    }
+    kern = W == 1 ? lds_kernel<1>(p->labeled) : W == 2 ? lds_kernel<2>(p->labeled) : W == 4 ? lds_kernel<4>(p->labeled) : lds_kernel<8>(p->labeled);
   }
-#undef PICK
-  if (lds > 64 * 1024) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return GTOK_E_LAUNCH;
-  }
-  int dev = 0, ncu = 256, occ = 1;
-  if (hipGetDevice(&dev) != hipSuccess) return GTOK_E_NO_DEVICE;
-  (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void *>(kern),
-                                                   wpb * 64, lds) != hipSuccess || occ < 1)
-    occ = 1;
+  if (lds > 64 * 1024 && !raise_lds_limit(reinterpret_cast<const void *>(kern), c.dev)) return GTOK_E_LAUNCH;
+  const int ncu = device_cu_count(c.dev);
+  int occ = occupancy_of(reinterpret_cast<const void *>(kern), c.dev, wpb * 64, lds);
+  if (occ < 1) occ = 1;
   a.queue = nullptr;
   QueueSlot slot;
   int nb;
@@ -391,18 +387,27 @@ static int sent_impl(const gtok_csr *g, const gtok_sent_params *p, int32_t *out_
     a.units = pairs; a.upb = 0;
     nb = ncu * occ;
     if (nb > a.units) nb = a.units;
-    slot = take_queue_slot(dev, (hipStream_t)stream);
+    slot = take_queue_slot(c.dev, c.stream);
     a.queue = slot.counters;
     if (!a.queue) return slot.graph_pool_empty ? GTOK_E_GRAPH_SLOTS : GTOK_E_LAUNCH;
   }
-  hipLaunchKernelGGL(kern, dim3(nb), dim3(wpb * 64), lds, (hipStream_t)stream, a);
-  mark_queue_slot(slot, (hipStream_t)stream);
+  hipLaunchKernelGGL(kern, dim3(nb), dim3(wpb * 64), lds, c.stream, a);
+  mark_queue_slot(slot, c.stream);
   return hipGetLastError() == hipSuccess ? GTOK_OK : GTOK_E_LAUNCH;
 }
 
-// ---------------------------------------------------------------------------------------------
-// adjacency bit-matrix mirror (include/gtok.h: gtok_csr_adjbits)
-// ---------------------------------------------------------------------------------------------
+int sent_impl(const gtok_csr *g, const gtok_sent_params *p, int32_t *out_ids, int32_t ld, int32_t *out_len,
+              const PackDest *pd, void *stream) {
+  gtok::DeviceScope device_scope((hipStream_t)stream);   // the stream's device, not the thread's current one
+  if (!device_scope.ok()) return GTOK_E_NO_DEVICE;
+  SentCall c{g, p, out_ids, ld, out_len, pd, (hipStream_t)stream, device_scope.dev};
+  const int rc = check_sent_args(c);
+  if (rc != GTOK_OK || c.which == SentKernel::None) return rc;       // (None: an empty batch)
+  return c.which == SentKernel::BLane ? launch_blane(c) : c.which == SentKernel::Lane ? launch_lane(c) : launch_wave(c);
+}
+
+}  // namespace
+
 extern "C" int gtok_sent(const gtok_csr *g, const gtok_sent_params *p, int32_t *out_ids,
                          int32_t ld, int32_t *out_len, void *stream) {
   return sent_impl(g, p, out_ids, ld, out_len, nullptr, stream);
@@ -422,6 +427,9 @@ extern "C" int64_t gtok_sent_pack_scratch_rows(void *stream) {
   return (int64_t)64 * 16 * device_cu_count(device_scope.dev);
 }
 
+// ---------------------------------------------------------------------------------------------
+// adjacency bit-matrix mirror (include/gtok.h: gtok_csr_adjbits)
+// ---------------------------------------------------------------------------------------------
 extern "C" int gtok_csr_adjbits(const gtok_csr *g, int32_t words, uint64_t *rows, uint64_t *planes, int32_t *info, void *stream) {
   gtok::DeviceScope device_scope((hipStream_t)stream);
   if (!device_scope.ok()) return GTOK_E_NO_DEVICE;
@@ -571,13 +579,13 @@ extern "C" int gtok_sent_decode(const int32_t *ids, int32_t ld, const int32_t *l
 extern "C" const char *gtok_sent_kernel_name(const gtok_csr *g, const gtok_sent_params *p) {
   if (!g || !p) return "";
   static const char *lds[] = {"sent_lds_kernel<W=1>", "sent_lds_kernel<W=2>", "sent_lds_kernel<W=4>", "sent_lds_kernel<W=8>"};
-  const int maxn = g->max_nodes > 0 ? g->max_nodes : 1;
   static const char *bl[] = {"sent_blane_kernel<W=1>", "sent_blane_kernel<W=2>", "sent_blane_kernel<W=4>"};
+  const int W = sent_words(sent_maxn(g)), wi = W == 8 ? 3 : W >> 1;   // 1, 2, 4, 8 -> 0, 1, 2, 3
   switch (choose_sent_kernel(g, p)) {
-    case -1: return "";
-    case 0: return "sent_lane_kernel";
-    case 1: return "sent_reg_kernel";
-    case 3: return bl[maxn <= 64 ? 0 : maxn <= 128 ? 1 : 2];
-    default: return lds[maxn <= 64 ? 0 : maxn <= 128 ? 1 : maxn <= 256 ? 2 : 3];
+    case SentKernel::None: return "";
+    case SentKernel::Lane: return "sent_lane_kernel";
+    case SentKernel::Reg: return "sent_reg_kernel";
+    case SentKernel::BLane: return bl[wi];      // (W <= 4: the mirror stops at 256 nodes)
+    default: return lds[wi];
   }
 }

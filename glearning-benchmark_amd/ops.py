@@ -111,10 +111,6 @@ def sent_safe_ld(batch: GraphBatch, labeled: bool, max_len: int, with_query: boo
     return (min(max_len, bound) + (3 if with_query else 0) + 15) // 16 * 16
 
 
-LANE_MIN_GRAPHS = 28000       # = GTOK_LANE_MIN_GRAPHS of gtok_sent.hip: from here on the molecule lane kernel takes small symmetric graphs
-ADJBITS_MIN_GRAPHS = 20000    # = GTOK_BLANE_MIN_GRAPHS of gtok_sent.hip: below it gtok_sent never picks the bit-matrix lane kernel
-
-
 def pack8(batch: GraphBatch) -> bool:
     """Give a device batch of small graphs its byte-packed rowptr / col mirror (gtok_csr_pack8; once per batch,
     kept on the batch object).  Returns whether the batch has one now.  A layout step like the CSR build: the
@@ -414,7 +410,7 @@ def adjbits(batch: GraphBatch) -> bool:
     if batch.col.device.type != "cuda" or batch.num_graphs == 0 or batch.max_nodes > 256:
         return False
     dev, G = batch.device, batch.num_graphs
-    W = 1 if batch.max_nodes <= 64 else 2 if batch.max_nodes <= 128 else 4
+    W = _adj_words(batch.max_nodes)
     total_nodes = batch.rowptr.numel() - G
     rows = torch.empty((max(total_nodes, 1), W), dtype=torch.int64, device=dev)
     planes = torch.empty((G, 8, W), dtype=torch.int64, device=dev)
@@ -527,117 +523,139 @@ def sent(batch: GraphBatch, max_num_nodes: int, max_len: int, seed: int, epoch: 
     if ld is None:
         ld = sent_safe_ld(batch, labeled, max_len, query is not None)
     G = batch.num_graphs
-    staging = None
-    if not slab:
-        if packed is None:
-            raise ValueError("slab=False goes with packed=")
-        ids = None
-        if out is not None:           # (staging rows of the caller's own - launches on several streams must not share the module's - , lengths)
-            staging, ln = out
-            if staging is not None and (staging.dtype != (torch.int16 if u16 else torch.int32) or not staging.is_contiguous()
-                                        or staging.device != torch.device(dev)):
-                raise ValueError("out[0] with slab=False: contiguous staging space of the rows' id width on the batch's device (or None)")
-            if ln.dtype != torch.int32 or ln.numel() != K * G or not ln.is_contiguous():
-                raise ValueError("out[1]: contiguous int32 [K * G]")
-        else:
-            ln = torch.empty((K * G,), dtype=torch.int32, device=dev)
-    elif out is not None:
-        ids, ln = out
-        want = torch.int16 if u16 else torch.int32
-        if ids.dtype != want or ln.dtype != torch.int32 or ids.numel() != K * G * ld or ln.numel() != K * G \
-                or not ids.is_contiguous() or not ln.is_contiguous() or ids.device != torch.device(dev) or (G and ids.shape[-1] != ld):
-            raise ValueError(f"out must be ({want} [K * G, ld] contiguous, int32 [K * G]) on the batch's device")
-    else:
-        ids = torch.empty((K * G, ld), dtype=torch.int16 if u16 else torch.int32, device=dev)
-        ln = torch.empty((K * G,), dtype=torch.int32, device=dev)
+    if not slab and packed is None:
+        raise ValueError("slab=False goes with packed=")
+    ids, staging, ln = _sent_out(out, slab, K, G, ld, u16, dev)
     if _lib.library_version() < 4 and (K > 1 or u16 or not pad):
         # (GTOK_LIB pointing at an ABI v3 build: it would ignore epoch_count and the row flags and write an int32 [G, ld] slab)
         raise _lib.GtokError(f"the loaded library has ABI version {_lib.library_version()}: epochs > 1, u16 and pad=False need version 4")
-    walks = G * K
-    if not batch.prepared:          # (a batch prepared by the caller - torch.ops.gtok.csr_prepare - is launched as it stands)
-        pack8(batch)
-        pin = os.environ.get("GTOK_SENT_KERNEL", "")
-        # the bit-matrix mirror is only built where gtok_sent would pick the kernel that reads it: unlabelled batches of
-        # >= ADJBITS_MIN_GRAPHS walks that the molecule kernel (<= 64 nodes, simple symmetric, >= LANE_MIN_GRAPHS) does not
-        # take - and never again for a batch that turned out unusable (a closure degree above 255)
-        lane_takes = batch.max_nodes <= 64 and batch.max_edges <= 255 and bool(batch.flags & _lib.CSR_SIMPLE_SYMMETRIC) \
-            and walks >= LANE_MIN_GRAPHS
-        wants_blane = pin == "blane" or (not pin and not labeled and not remap_zinc and walks >= ADJBITS_MIN_GRAPHS and not lane_takes)
-        if wants_blane and not batch.adj_unusable:
-            if adjbits(batch):
-                if os.environ.get("GTOK_BLANE_ORDER", "1") != "0" and batch.lane_order_len != max(1, max_len):
-                    batch.lane_order, batch.lane_order_len = _lane_order(batch, max(1, max_len)), max(1, max_len)   # once per (batch, max_len)
-            elif batch.col.device.type == "cuda" and batch.max_nodes <= 256 and os.environ.get("GTOK_NO_ADJBITS") != "1":
-                batch.adj_unusable = True
-    flags = (0 if pad else _lib.SENT_NO_PAD) | (_lib.SENT_U16 if u16 else 0)
-    p = GtokSentParams(max_num_nodes, int(labeled), num_node_types, num_edge_types, max_len, int(remap_zinc),
-                       pad_id, flags, seed & (2 ** 64 - 1), epoch & (2 ** 64 - 1), graph_base,
-                       None if query is None else query.data_ptr(), K, 0)
-    cs = batch.c_struct()
-    if os.environ.get("GTOK_NO_LANE_SORT") != "1" and batch.graph_ids is None and not batch.prepared \
-            and lib().gtok_sent_kernel_name(ctypes.byref(cs), ctypes.byref(p)) == b"sent_lane_kernel":
-        sb = lane_sorted(batch)                                       # once per resident batch
-        if sb is not None:
-            cs = sb.c_struct()
+    params = lambda flags: _sent_params(max_num_nodes, max_len, labeled, num_node_types, num_edge_types, remap_zinc, pad_id, flags,
+                                        seed, epoch, graph_base, query, K)
+    p = params((0 if pad else _lib.SENT_NO_PAD) | (_lib.SENT_U16 if u16 else 0))
+    cs = _sent_layouts(batch, p, max_len)
     global _LAST_SENT
     _LAST_SENT = (cs, p)
-    rc = _lib.E_UNSUPPORTED
-    if packed is not None:
-        if _lib.library_version() < 6:
-            raise _lib.GtokError(f"the loaded library has ABI version {_lib.library_version()}: packed= needs version 6")
-        pk8 = packed.buf.dtype == torch.uint8
-        if pk8 and not u16:
-            raise ValueError("packed: 8-bit packed rows go with u16=True (the slab / staging rows stay 16-bit)")
-        if pk8 and _lib.library_version() < 8:
-            raise _lib.GtokError(f"the loaded library has ABI version {_lib.library_version()}: 8-bit packed rows need version 8")
-        if (not pk8 and packed.buf.dtype != (torch.int16 if u16 else torch.int32)) or packed.row_start.numel() < K * G or packed.buf.device != ln.device:
-            raise ValueError("packed: a PackedRows of this launch's rows, id width and device")
-        packed._fresh_state()
-        if pk8:
-            flags |= _lib.SENT_PACK_U8          # (gtok_sent_packed only: the plain launch below gets p, built before)
-        if G and ld % (16 if pk8 else 8 if u16 else 4) == 0:
-            dst, pp = ids, p
-            if pk8 and slab:
-                pp = GtokSentParams(max_num_nodes, int(labeled), num_node_types, num_edge_types, max_len, int(remap_zinc), pad_id,
-                                    flags, seed & (2 ** 64 - 1), epoch & (2 ** 64 - 1), graph_base,
-                                    None if query is None else query.data_ptr(), K, 0)
-            if not slab:
-                need = int(lib().gtok_sent_pack_scratch_rows(_stream(dev))) * ld
-                if staging is not None and staging.numel() < need:
-                    raise ValueError(f"out[0] with slab=False: {need} ids of staging space (gtok_sent_pack_scratch_rows() x ld)")
-                dst = staging if staging is not None else _pack_scratch(dev, ld, u16)
-                pp = GtokSentParams(max_num_nodes, int(labeled), num_node_types, num_edge_types, max_len, int(remap_zinc), pad_id,
-                                    flags | _lib.SENT_PACK_ONLY, seed & (2 ** 64 - 1), epoch & (2 ** 64 - 1), graph_base,
-                                    None if query is None else query.data_ptr(), K, 0)
-            rc = lib().gtok_sent_packed(ctypes.byref(cs), ctypes.byref(pp), dst.data_ptr(), ld, ln.data_ptr(), packed.buf.data_ptr(),
-                                        packed.capacity, packed.row_start.data_ptr(), packed.state.data_ptr(), _stream(dev))
-            if rc != _lib.E_UNSUPPORTED:
-                check(rc, "gtok_sent_packed")
-        packed.fused = rc == 0
+    rc = _lib.E_UNSUPPORTED if packed is None else _sent_packed(cs, p, params, packed, ids, staging, ln, K * G, ld, u16, dev)
     if rc == _lib.E_UNSUPPORTED:
         if ids is None:             # another kernel walks: it needs the slab after all (a temporary one)
             ids = torch.empty((K * G, ld), dtype=torch.int16 if u16 else torch.int32, device=dev)
         check(lib().gtok_sent(ctypes.byref(cs), ctypes.byref(p), ids.data_ptr(), ld, ln.data_ptr(), _stream(dev)),
               "gtok_sent")
         if packed is not None and G:           # another kernel walked: the one-pass pack behind it (dataset order)
-            ptr = torch.empty(K * G + 1, dtype=torch.int64, device=dev)
-            st = torch.empty(1, dtype=torch.int32, device=dev)
-            eb = 2 if u16 else 4
-            pb = packed.buf.element_size()          # (1: 8-bit packed rows from the 16-bit slab, 16-id alignment)
-            check(lib().gtok_pack_rows_scan(ids.data_ptr(), eb, ld, ln.data_ptr(), K * G, 16 if pb == 1 else 8, pb, packed.buf.data_ptr(), packed.capacity,
-                                            ptr.data_ptr(), st.data_ptr(), _stream(dev)), "gtok_pack_rows_scan")
-            # a row the scan skipped keeps its offset in ptr: it is marked -1 here, as the fused route marks it
-            skipped = ptr[:-1] + ln.clamp(0, ld) > packed.capacity
-            packed.row_start[:K * G].copy_(torch.where(skipped, -1, ptr[:-1]))
-            packed.state[PACK_STATE_FILL:PACK_STATE_FILL + 1].copy_(ptr[-1:])
-            packed.state[0:1].copy_(st.to(torch.int64) & (3 if pb == 1 else 2))
+            _pack_behind_walk(packed, ids, ln, K * G, ld, dev)
     if packed is not None and packed.buf.dtype == torch.uint8 and check_ids and G and not torch.cuda.is_current_stream_capturing():
         packed.verify()
-    if not slab:
-        return None, (ln.view(K, G) if K > 1 else ln.view(G))
-    if K > 1:
-        return ids.view(K, G, ld), ln.view(K, G)
-    return ids.view(G, ld), ln.view(G)
+    shape = (K, G) if K > 1 else (G,)
+    return (ids.view(*shape, ld) if slab else None), ln.view(shape)
+
+
+def _sent_params(max_num_nodes: int, max_len: int, labeled: bool, num_node_types: int, num_edge_types: int, remap_zinc: bool,
+                 pad_id: int = SENT_PAD, flags: int = 0, seed: int = 0, epoch: int = 0, graph_base: int = 0,
+                 query: Optional[torch.Tensor] = None, epochs: int = 1) -> GtokSentParams:
+    """include/gtok.h: gtok_sent_params of a call's arguments and a flags word (GTOK_SENT_*)."""
+    return GtokSentParams(max_num_nodes, int(labeled), num_node_types, num_edge_types, max_len, int(remap_zinc), pad_id, flags,
+                          seed & (2 ** 64 - 1), epoch & (2 ** 64 - 1), graph_base, None if query is None else query.data_ptr(),
+                          max(1, int(epochs)), 0)
+
+
+def _sent_out(out, slab: bool, K: int, G: int, ld: int, u16: bool, dev):
+    """(slab or None, the caller's own staging rows or None, lengths) of a sent() call: allocated, or the caller's `out` validated."""
+    want = torch.int16 if u16 else torch.int32
+    if out is None:
+        return (torch.empty((K * G, ld), dtype=want, device=dev) if slab else None), None, torch.empty((K * G,), dtype=torch.int32, device=dev)
+    if slab:
+        ids, ln = out
+        if ids.dtype != want or ln.dtype != torch.int32 or ids.numel() != K * G * ld or ln.numel() != K * G \
+                or not ids.is_contiguous() or not ln.is_contiguous() or ids.device != torch.device(dev) or (G and ids.shape[-1] != ld):
+            raise ValueError(f"out must be ({want} [K * G, ld] contiguous, int32 [K * G]) on the batch's device")
+        return ids, None, ln
+    staging, ln = out         # (staging rows of the caller's own - launches on several streams must not share the module's - , lengths)
+    if staging is not None and (staging.dtype != want or not staging.is_contiguous() or staging.device != torch.device(dev)):
+        raise ValueError("out[0] with slab=False: contiguous staging space of the rows' id width on the batch's device (or None)")
+    if ln.dtype != torch.int32 or ln.numel() != K * G or not ln.is_contiguous():
+        raise ValueError("out[1]: contiguous int32 [K * G]")
+    return None, staging, ln
+
+
+def _adj_words(max_nodes: int) -> int:        # 64-bit words of a row of the adjacency bit-matrix mirror (<= 256 nodes)
+    return 1 if max_nodes <= 64 else 2 if max_nodes <= 128 else 4
+
+
+def _mirror_wanted(cs: _lib.GtokCsr, p: GtokSentParams) -> bool:
+    """Whether gtok_sent would launch sent_blane_kernel if the batch had its bit-matrix mirror: the launcher's own choice (GTOK_SENT_KERNEL
+    included) for a copy of the C struct that claims one as adjbits() builds it.  (Scalars alone are read: the claim is never dereferenced.)"""
+    claim = _lib.GtokCsr.from_buffer_copy(cs)
+    claim.adj_rows = claim.adj_planes = 1
+    claim.adj_words, claim.adj_max_degree = _adj_words(cs.max_nodes), 0
+    return lib().gtok_sent_kernel_name(ctypes.byref(claim), ctypes.byref(p)).startswith(b"sent_blane_kernel")
+
+
+def _sent_layouts(batch: GraphBatch, p: GtokSentParams, max_len: int) -> _lib.GtokCsr:
+    """The C struct sent() launches: the batch with the layouts its kernel reads, each built on first use and kept on the batch."""
+    if not batch.prepared:          # (a batch prepared by the caller - torch.ops.gtok.csr_prepare - is launched as it stands)
+        pack8(batch)
+        # the bit-matrix mirror is only built where gtok_sent would pick the kernel that reads it - and never again for a batch
+        # that turned out unusable (a closure degree above 255)
+        if not batch.adj_unusable and _mirror_wanted(batch.c_struct(), p):
+            if adjbits(batch):
+                if os.environ.get("GTOK_BLANE_ORDER", "1") != "0" and batch.lane_order_len != max(1, max_len):
+                    batch.lane_order, batch.lane_order_len = _lane_order(batch, max(1, max_len)), max(1, max_len)   # once per (batch, max_len)
+            elif batch.col.device.type == "cuda" and batch.max_nodes <= 256 and os.environ.get("GTOK_NO_ADJBITS") != "1":
+                batch.adj_unusable = True
+    cs = batch.c_struct()
+    if os.environ.get("GTOK_NO_LANE_SORT") != "1" and batch.graph_ids is None and not batch.prepared \
+            and lib().gtok_sent_kernel_name(ctypes.byref(cs), ctypes.byref(p)) == b"sent_lane_kernel":
+        sb = lane_sorted(batch)                                       # once per resident batch
+        if sb is not None:
+            cs = sb.c_struct()
+    return cs
+
+
+def _sent_packed(cs, p: GtokSentParams, params, packed: PackedRows, ids, staging, ln, rows: int, ld: int, u16: bool, dev) -> int:
+    """sent(packed=): gtok_sent_packed - the walk packs its rows.  Returns 0, or GTOK_E_UNSUPPORTED where it cannot (another kernel, no rows,
+    an ld that is not whole 16-byte pieces).  ids None (slab=False): the rows are staged in `staging` or the module's scratch (GTOK_SENT_PACK_ONLY)."""
+    if _lib.library_version() < 6:
+        raise _lib.GtokError(f"the loaded library has ABI version {_lib.library_version()}: packed= needs version 6")
+    pk8 = packed.buf.dtype == torch.uint8
+    if pk8 and not u16:
+        raise ValueError("packed: 8-bit packed rows go with u16=True (the slab / staging rows stay 16-bit)")
+    if pk8 and _lib.library_version() < 8:
+        raise _lib.GtokError(f"the loaded library has ABI version {_lib.library_version()}: 8-bit packed rows need version 8")
+    if (not pk8 and packed.buf.dtype != (torch.int16 if u16 else torch.int32)) or packed.row_start.numel() < rows or packed.buf.device != ln.device:
+        raise ValueError("packed: a PackedRows of this launch's rows, id width and device")
+    packed._fresh_state()
+    rc, flags = _lib.E_UNSUPPORTED, p.flags
+    if rows and ld % (16 if pk8 else 8 if u16 else 4) == 0:
+        if pk8:
+            flags |= _lib.SENT_PACK_U8
+        dst = ids
+        if ids is None:
+            need = int(lib().gtok_sent_pack_scratch_rows(_stream(dev))) * ld
+            if staging is not None and staging.numel() < need:
+                raise ValueError(f"out[0] with slab=False: {need} ids of staging space (gtok_sent_pack_scratch_rows() x ld)")
+            dst = staging if staging is not None else _pack_scratch(dev, ld, u16)
+            flags |= _lib.SENT_PACK_ONLY
+        pp = p if flags == p.flags else params(flags)
+        rc = lib().gtok_sent_packed(ctypes.byref(cs), ctypes.byref(pp), dst.data_ptr(), ld, ln.data_ptr(), packed.buf.data_ptr(),
+                                    packed.capacity, packed.row_start.data_ptr(), packed.state.data_ptr(), _stream(dev))
+        if rc != _lib.E_UNSUPPORTED:
+            check(rc, "gtok_sent_packed")
+    packed.fused = rc == 0
+    return rc
+
+
+def _pack_behind_walk(packed: PackedRows, ids: torch.Tensor, ln: torch.Tensor, rows: int, ld: int, dev) -> None:
+    """sent(packed=) behind a kernel that does not pack: gtok_pack_rows_scan over the slab, described in `packed` as the fused route does."""
+    ptr = torch.empty(rows + 1, dtype=torch.int64, device=dev)
+    st = torch.empty(1, dtype=torch.int32, device=dev)
+    pb = packed.buf.element_size()          # (1: 8-bit packed rows from the 16-bit slab, 16-id alignment)
+    check(lib().gtok_pack_rows_scan(ids.data_ptr(), ids.element_size(), ld, ln.data_ptr(), rows, 16 if pb == 1 else 8, pb, packed.buf.data_ptr(),
+                                    packed.capacity, ptr.data_ptr(), st.data_ptr(), _stream(dev)), "gtok_pack_rows_scan")
+    # a row the scan skipped keeps its offset in ptr: it is marked -1 here, as the fused route marks it
+    skipped = ptr[:-1] + ln.clamp(0, ld) > packed.capacity
+    packed.row_start[:rows].copy_(torch.where(skipped, -1, ptr[:-1]))
+    packed.state[PACK_STATE_FILL:PACK_STATE_FILL + 1].copy_(ptr[-1:])
+    packed.state[0:1].copy_(st.to(torch.int64) & (3 if pb == 1 else 2))
 
 
 _PACK_SCRATCH = {}
@@ -672,8 +690,7 @@ def last_sent_kernel() -> str:
 def sent_kernel_name(batch: GraphBatch, max_num_nodes: int, max_len: int, labeled: bool = False, num_node_types: int = 0,
                      num_edge_types: int = 0, remap_zinc: bool = False, epochs: int = 1) -> str:
     """Name of the kernel gtok_sent() picks for this batch (for profiles and bench labels)."""
-    p = GtokSentParams(max_num_nodes, int(labeled), num_node_types, num_edge_types, max_len, int(remap_zinc), SENT_PAD,
-                       0, 0, 0, 0, None, max(1, int(epochs)), 0)
+    p = _sent_params(max_num_nodes, max_len, labeled, num_node_types, num_edge_types, remap_zinc, epochs=epochs)
     cs = batch.c_struct()
     return lib().gtok_sent_kernel_name(ctypes.byref(cs), ctypes.byref(p)).decode()
 
