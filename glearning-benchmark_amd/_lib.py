@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 # GTOK_LIB: load another build of the same ABI (profiling builds of profiles/tools, e.g. -DGTOK_PHASE_TIMING)
 LIB_PATH = os.environ.get("GTOK_LIB") or os.path.join(_HERE, "csrc", "libgtok.so")
-SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("gtok_sent.hip", "gtok_ibtt.hip", "gtok_rows.hip", "gtok_csr.hip")]
+SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("gtok_sent.hip", "gtok_sent_large.hip", "gtok_ibtt.hip", "gtok_rows.hip", "gtok_csr.hip")]
 HEADERS = [os.path.join(_HERE, "csrc", "gtok_common.hpp"), os.path.join(_HERE, "csrc", "gtok_sent_blane.hpp"), os.path.join(_HERE, "csrc", "gtok_sent_reg.hpp"), os.path.join(_HERE, "csrc", "gtok_sent_lds.hpp"),
            os.path.join(_HERE, "csrc", "gtok_sent_lane.hpp"),
            os.path.join(_ROOT, "include", "gtok.h")]
@@ -44,6 +44,8 @@ SENT_NO_PAD = 1
 SENT_U16 = 2
 SENT_PACK_ONLY = 4
 SENT_PACK_U8 = 8
+SENT_LARGE_MAX_NODES = 16384    # include/gtok.h: GTOK_SENT_LARGE_MAX_NODES
+SENT_LARGE_WAVES = 1024         # include/gtok.h: GTOK_SENT_LARGE_WAVES
 
 
 class GtokCsrSorted(ctypes.Structure):
@@ -99,6 +101,8 @@ SYMBOLS = {
     "gtok_ibtt_synth": (_I, [ctypes.POINTER(GtokCsr), _P, _I, _P, _I, _I, _P, _I, _P, _P]),
     "gtok_text_to_ids": (_I, [_P, _P, _I, ctypes.POINTER(GtokVocabTable), _I, _I, _P, _I, _P, _P]),
     "gtok_sent": (_I, [ctypes.POINTER(GtokCsr), ctypes.POINTER(GtokSentParams), _P, _I, _P, _P]),
+    "gtok_sent_large_workspace": (ctypes.c_int64, [_I, _I, ctypes.c_int64]),
+    "gtok_sent_large": (_I, [ctypes.POINTER(GtokCsr), ctypes.POINTER(GtokSentParams), _P, _I, _P, _P, ctypes.c_int64, _P]),
     "gtok_sent_packed": (_I, [ctypes.POINTER(GtokCsr), ctypes.POINTER(GtokSentParams), _P, _I, _P, _P, ctypes.c_int64, _P, _P, _P]),
     "gtok_sent_pack_scratch_rows": (ctypes.c_int64, [_P]),
     "gtok_unpack_rows_at": (_I, [_P, _I, _P, _P, ctypes.c_int64, _I, ctypes.c_int64, ctypes.c_int64, _I, _P, _I, _I, _P, _P]),
@@ -135,6 +139,10 @@ SYMBOLS = {
     "gtok_version": (_I, []),
     "gtok_target": (ctypes.c_char_p, []),
 }
+
+# entry points added without an ABI version step (include/gtok.h): a library of the same version may lack them (GTOK_LIB pointing
+# at an earlier build) - they are bound when the loaded library has the symbol, and callers ask hasattr(lib(), name)
+OPTIONAL_SYMBOLS = ("gtok_sent_large_workspace", "gtok_sent_large")
 
 ERRORS = {-1: "GTOK_E_INVAL", -2: "GTOK_E_TOO_LARGE", -3: "GTOK_E_LAUNCH", -4: "GTOK_E_NO_DEVICE", -5: "GTOK_E_GRAPH_SLOTS", -6: "GTOK_E_UNSUPPORTED"}
 E_UNSUPPORTED = -6
@@ -211,7 +219,7 @@ def lib() -> ctypes.CDLL:
         # (library_version() gates the inputs an older library would silently ignore: ops.sent)
         older_ok = bool(os.environ.get("GTOK_LIB")) and 3 <= h.gtok_version() < ABI_VERSION
         for name, (res, args) in SYMBOLS.items():
-            if older_ok and not hasattr(h, name):
+            if (older_ok or name in OPTIONAL_SYMBOLS) and not hasattr(h, name):
                 continue
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args

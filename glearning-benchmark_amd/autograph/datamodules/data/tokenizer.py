@@ -91,6 +91,11 @@ class Graph2TrailTokenizer:
         if self.max_num_nodes is None:
             raise RuntimeError("call set_num_nodes() first")
         self.launches += 1
+        if batch.max_nodes > _ops.SENT_MAX_NODES:      # beyond gtok_sent's kernels: gtok_sent_large, same tokens
+            return _ops.sent_large(batch, self.max_num_nodes, self._max_len(), self.seed, epoch, labeled=self.labeled_graph,
+                                   num_node_types=self.num_node_types, num_edge_types=self.num_edge_types,
+                                   remap_zinc=remap_zinc, pad_id=self.pad, graph_base=graph_base, query=query, ld=ld, out=out,
+                                   pad=pad, epochs=epochs, u16=u16)
         return _ops.sent(batch, self.max_num_nodes, self._max_len(), self.seed, epoch, labeled=self.labeled_graph,
                          num_node_types=self.num_node_types, num_edge_types=self.num_edge_types,
                          remap_zinc=remap_zinc, pad_id=self.pad, graph_base=graph_base, query=query, ld=ld, out=out, pad=pad,

@@ -16,6 +16,7 @@ from ._lib import GtokSentParams, GtokVocabTable, check, lib
 from .csr import GraphBatch
 
 SENT_SOS, SENT_RESET, SENT_LADJ, SENT_RADJ, SENT_EOS, SENT_PAD, SENT_IDX_OFFSET = 0, 1, 2, 3, 4, 5, 6
+SENT_MAX_NODES = 512        # include/gtok.h: GTOK_MAX_NODES - the largest graph gtok_sent walks (sent_large: _lib.SENT_LARGE_MAX_NODES)
 
 ZINC_ATOM_SYMBOLS = ("C", "N", "O", "F", "P", "S", "Cl", "Br", "I", "X")
 ZINC_BOND_NAMES = ("unknown", "single", "double", "triple", "aromatic")
@@ -549,6 +550,58 @@ def sent(batch: GraphBatch, max_num_nodes: int, max_len: int, seed: int, epoch: 
     return (ids.view(*shape, ld) if slab else None), ln.view(shape)
 
 
+_LARGE_WS = {}
+
+
+def _large_workspace(dev, need: int) -> torch.Tensor:
+    """gtok_sent_large's workspace: one uint8 buffer per device, grown on demand, shared by every launch on that device (launches on
+    one stream follow each other; its contents mean nothing between launches)."""
+    key = torch.device(dev).index or 0
+    t = _LARGE_WS.get(key)
+    if t is None or t.numel() < need:
+        t = torch.empty(max(16, need), dtype=torch.uint8, device=dev)
+        _LARGE_WS[key] = t
+    return t
+
+
+def sent_large(batch: GraphBatch, max_num_nodes: int, max_len: int, seed: int, epoch: int = 0, labeled: bool = False,
+               num_node_types: int = 0, num_edge_types: int = 0, remap_zinc: bool = False, pad_id: int = SENT_PAD,
+               graph_base: int = 0, query: Optional[torch.Tensor] = None, ld: Optional[int] = None, out=None, pad: bool = True,
+               epochs: int = 1, u16: bool = False, workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """gtok_sent_large: the SENT trail walk for batches ops.sent refuses - graphs of up to _lib.SENT_LARGE_MAX_NODES nodes, any edge
+    list (one direction or both, duplicates, self loops), in dataset order.  Same tokens, same keywords and same returns as
+    ops.sent (minus packed= / slab=: packed rows of such batches come from ops.pack_rows_scan over the slab).  workspace: a
+    uint8 tensor of the caller's own (launches on several streams must not share the module's); None = a cached one per device."""
+    _need_gpu(batch.col, "sent_large")
+    if not hasattr(lib(), "gtok_sent_large"):
+        raise _lib.GtokError("the loaded library has no gtok_sent_large: rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
+    dev = batch.device
+    K = max(1, int(epochs))
+    if query is not None:
+        query = query.to(dev, dtype=torch.int32).contiguous()
+        if tuple(query.shape) != (batch.num_graphs, 2):
+            raise ValueError("query must be [G, 2] (query_u, query_v)")
+    if ld is None:
+        ld = sent_safe_ld(batch, labeled, max_len, query is not None)
+    G = batch.num_graphs
+    ids, _, ln = _sent_out(out, True, K, G, ld, u16, dev)
+    p = _sent_params(max_num_nodes, max_len, labeled, num_node_types, num_edge_types, remap_zinc, pad_id,
+                     (0 if pad else _lib.SENT_NO_PAD) | (_lib.SENT_U16 if u16 else 0), seed, epoch, graph_base, query, K)
+    cs = batch.c_struct()
+    need = int(lib().gtok_sent_large_workspace(batch.max_nodes, batch.max_edges, G * K))
+    if need < 0:
+        check(need, "gtok_sent_large_workspace")
+    ws = workspace if workspace is not None else _large_workspace(dev, need)
+    if ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.device != torch.device(dev):
+        raise ValueError("workspace: a contiguous uint8 tensor on the batch's device")
+    check(lib().gtok_sent_large(ctypes.byref(cs), ctypes.byref(p), ids.data_ptr(), ld, ln.data_ptr(), ws.data_ptr(), ws.numel(),
+                                _stream(dev)), "gtok_sent_large")
+    global _LAST_SENT
+    _LAST_SENT = "sent_large_kernel"
+    shape = (K, G) if K > 1 else (G,)
+    return ids.view(*shape, ld), ln.view(shape)
+
+
 def _sent_params(max_num_nodes: int, max_len: int, labeled: bool, num_node_types: int, num_edge_types: int, remap_zinc: bool,
                  pad_id: int = SENT_PAD, flags: int = 0, seed: int = 0, epoch: int = 0, graph_base: int = 0,
                  query: Optional[torch.Tensor] = None, epochs: int = 1) -> GtokSentParams:
@@ -680,9 +733,11 @@ _LAST_SENT = None
 
 def last_sent_kernel() -> str:
     """Name of the kernel the most recent ops.sent call of this process launched (tests, bench labels): what the C ABI's
-    gtok_sent_kernel_name answers for the very structs that call passed to gtok_sent."""
+    gtok_sent_kernel_name answers for the very structs that call passed to gtok_sent ("sent_large_kernel" after ops.sent_large)."""
     if _LAST_SENT is None:
         return ""
+    if isinstance(_LAST_SENT, str):
+        return _LAST_SENT
     cs, p = _LAST_SENT
     return lib().gtok_sent_kernel_name(ctypes.byref(cs), ctypes.byref(p)).decode()
 

@@ -238,6 +238,32 @@ _FRAG.impl("sent", sent, "CUDA")
 torch.library.register_fake("gtok::sent", _sent_fake, lib=_FRAG)
 
 
+def sent_large(node_ptr: Tensor, edge_ptr: Tensor, rowptr: Tensor, col: Tensor, nattr: Optional[Tensor],
+               eattr: Optional[Tensor], query: Optional[Tensor], max_nodes: int, max_edges: int, max_num_nodes: int,
+               max_len: int, ld: int, seed: int, epoch: int, labeled: bool, num_node_types: int, num_edge_types: int,
+               remap_zinc: bool, pad_id: int, graph_base: int) -> Tuple[Tensor, Tensor]:
+    """gtok_sent_large: gtok::sent for batches of graphs of more than 512 nodes (any edge list, dataset order).  The batch behind
+    these tensors is verified on the device on the first call (a batch that proves simple and symmetric skips the in-lists) and
+    found again on later calls with the SAME tensor objects."""
+    b = _batch(node_ptr, edge_ptr, rowptr, col, None, nattr, eattr, max_nodes, max_edges, verify=True)
+    return _ops.sent_large(b, max_num_nodes, max_len, seed, epoch, labeled=labeled, num_node_types=num_node_types,
+                           num_edge_types=num_edge_types, remap_zinc=remap_zinc, pad_id=pad_id, graph_base=graph_base,
+                           query=query, ld=ld)
+
+
+def _sent_large_fake(node_ptr, edge_ptr, rowptr, col, nattr, eattr, query, max_nodes, max_edges, max_num_nodes, max_len, ld, seed,
+                     epoch, labeled, num_node_types, num_edge_types, remap_zinc, pad_id, graph_base):
+    G = node_ptr.shape[0] - 1
+    return node_ptr.new_empty((G, ld), dtype=torch.int32), node_ptr.new_empty((G,), dtype=torch.int32)
+
+
+_FRAG.define("sent_large(Tensor node_ptr, Tensor edge_ptr, Tensor rowptr, Tensor col, Tensor? nattr, Tensor? eattr, Tensor? query, "
+             "int max_nodes, int max_edges, int max_num_nodes, int max_len, int ld, int seed, int epoch, bool labeled, int num_node_types, "
+             "int num_edge_types, bool remap_zinc, int pad_id, int graph_base) -> (Tensor, Tensor)")
+_FRAG.impl("sent_large", sent_large, "CUDA")
+torch.library.register_fake("gtok::sent_large", _sent_large_fake, lib=_FRAG)
+
+
 def sent_epochs(node_ptr: Tensor, edge_ptr: Tensor, rowptr: Tensor, col: Tensor, nattr: Optional[Tensor],
                 eattr: Optional[Tensor], query: Optional[Tensor], max_nodes: int, max_edges: int, max_num_nodes: int,
                 max_len: int, ld: int, seed: int, epoch: int, epochs: int, labeled: bool, num_node_types: int, num_edge_types: int,

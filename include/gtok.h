@@ -17,6 +17,8 @@
  *                      trainer/train_agtt.py:250 (SENT walk; spec in DESIGN.md,
  *                      upstream parity unpinned), optionally fused with
  *                      remap_zinc_tokens (:171-244) and the query append (:257-267)
+ *   gtok_sent_large    gtok_sent for batches it refuses: graphs of up to GTOK_SENT_LARGE_MAX_NODES nodes (the protein graphs and
+ *                      point clouds of the model family), any edge list, with a caller-given workspace - same tokens
  *   gtok_sent_packed   gtok_sent whose walk also appends every row to a packed buffer (the payload of the all-gather behind the
  *                      val / test loaders, trainer/train_agtt.py:602-607, and of the D2H copy behind :246-273) - no second pass
  *   gtok_sent_decode   the SENT spec read backwards (token rows -> graphs in visit-index space)
@@ -108,7 +110,7 @@ extern "C" {
                                    use the two-call route (gtok_sent + gtok_pack_rows_scan).  Still ABI version 8: callers
                                    learn what a library packs in the walk from this code                                       */
 
-#define GTOK_MAX_NODES 512 /* SENT adjacency bit-matrix rows per wave (LDS)  */
+#define GTOK_MAX_NODES 512 /* SENT adjacency bit-matrix rows per wave (LDS): gtok_sent / gtok_sent_packed only - gtok_sent_large walks larger graphs */
 
 /* flags: properties the CALLER has verified for the whole batch (on the host, or with gtok_csr_check on the device) */
 #define GTOK_CSR_SIMPLE_SYMMETRIC 1 /* simple undirected graphs, both directions stored: no self-loop, no entry
@@ -395,6 +397,35 @@ typedef struct gtok_sent_params {
  * that of K calls with epoch, epoch + 1, ... written to consecutive [G, ld] slices.                               */
 int gtok_sent(const gtok_csr *g, const gtok_sent_params *p, int32_t *out_ids,
               int32_t ld, int32_t *out_len, void *stream);
+
+/* ---- gtok_sent_large: the SENT walk for graphs of more than GTOK_MAX_NODES nodes -------------------------------------------
+ * Same spec, same tokens, same output convention as gtok_sent (bit-exact against oracle_sent), for ANY batch in dataset order
+ * whose largest graph has at most GTOK_SENT_LARGE_MAX_NODES nodes - small graphs included, so a caller need not split a
+ * batch.  Any edge list: one direction or both (the walk forms the symmetric closure itself - the graph-token datasets list
+ * every edge once, graph_token_dataset_autograph.py:336-348), duplicates, self loops, unsorted rows; with or without
+ * GTOK_CSR_SIMPLE_SYMMETRIC (with it the walk skips building the lists of entries that name a node from other rows), labelled
+ * or not.  Honours remap_zinc, query, graph_base, epoch_count = K ([K, G, ld], epoch-major), GTOK_SENT_NO_PAD and GTOK_SENT_U16
+ * (GTOK_E_TOO_LARGE when an id cannot fit 16 bits, gtok_sent's rule: 6 + max_num_nodes + num_node_types + 512 <= 65535).
+ * out_len is the true length cut at max_len (max_len beyond 0x70000000 reads as that): the walk keeps counting past ld.
+ * One wave walks one (graph, epoch) pair; a launch has at most GTOK_SENT_LARGE_WAVES waves and wave w takes pairs w,
+ * w + waves, ... - `workspace` holds one slice per wave (12 bytes per node + 8 per entry of the batch's maxima):
+ * gtok_sent_large_workspace(max_nodes, max_edges, num_graphs x epochs) bytes of device memory, 16-byte aligned, contents
+ * unspecified before and after, free again when the stream has run the call.  The call only enqueues on `stream`: no
+ * allocation, no host synchronisation, no library-owned counters.
+ * Errors, all before anything is launched: GTOK_E_INVAL for null pointers / bad sizes, a reordered batch (graph_ids / unit_ptr
+ * set), labelled without attributes, GTOK_SENT_PACK_ONLY / GTOK_SENT_PACK_U8, a workspace that is misaligned or smaller than
+ * gtok_sent_large_workspace() says; GTOK_E_TOO_LARGE for max_nodes beyond GTOK_SENT_LARGE_MAX_NODES.  An entry with an endpoint
+ * outside [0, N_g) is skipped (as the oracle does); a graph whose real N or E exceeds the batch's max_nodes / max_edges is
+ * clamped to them: wrong tokens, never an access outside its slice or its row.  Packed rows of such batches come from
+ * gtok_pack_rows_scan over the slab.  (Added without an ABI version step, like GTOK_E_UNSUPPORTED: no struct changes - a
+ * binding learns that a library has it from the symbol.)
+ * gtok_sent_large_workspace: pure host arithmetic (no device, no pointer is touched); a multiple of 16; GTOK_E_INVAL for a
+ * negative argument, GTOK_E_TOO_LARGE beyond GTOK_SENT_LARGE_MAX_NODES.                                                     */
+#define GTOK_SENT_LARGE_MAX_NODES 16384 /* largest graph gtok_sent_large walks */
+#define GTOK_SENT_LARGE_WAVES 1024      /* most walks in flight in one launch: the workspace holds one slice per wave */
+int64_t gtok_sent_large_workspace(int32_t max_nodes, int32_t max_edges, int64_t walks);
+int gtok_sent_large(const gtok_csr *g, const gtok_sent_params *p, int32_t *out_ids, int32_t ld, int32_t *out_len,
+                    void *workspace, int64_t workspace_bytes, void *stream);
 
 /* gtok_sent whose walk ALSO appends every row to a packed buffer (ABI v6): the payload of the compact all-gather and of the
  * per-epoch D2H copy without a second pass over the rows.  `packed` holds `capacity` ids of the slab's width (16-bit with
