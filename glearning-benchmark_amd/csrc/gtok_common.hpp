@@ -13,6 +13,9 @@
 #include <atomic>
 #include <cstdlib>
 #include <mutex>
+#include <type_traits>
+
+#include "gtok.h"
 
 namespace gtok {
 
@@ -22,24 +25,13 @@ constexpr int kWave = 64;
 // floor(800 / (ceil(sgpr/16)*16 + 16)) = 6 waves per SIMD while hipOccupancyMaxActiveBlocksPerMultiprocessor
 // answers 8 (MI355X_MICROARCH.md, "Residency and cooperative launch"); a grid sized by the API's answer runs
 // a straggler second round (measured: 0.72 ms at 8 vs 0.65 ms at 6).  GTOK_MAX_BLOCKS_PER_CU overrides.
-inline int resident_blocks(int api_answer) {
-  int cap = 6;
-  if (const char *s = std::getenv("GTOK_MAX_BLOCKS_PER_CU")) {
-    const int c = std::atoi(s);
-    if (c >= 1) cap = c;
-  }
+inline int capped(int api_answer, const char *env, int cap) {
+  if (const char *s = std::getenv(env)) { const int c = std::atoi(s); if (c >= 1) cap = c; }
   return api_answer < cap ? api_answer : cap;
 }
-
+inline int resident_blocks(int api_answer) { return capped(api_answer, "GTOK_MAX_BLOCKS_PER_CU", 6); }
 // same limit for kernels launched as one-wave workgroups: 4 SIMDs x 6 waves
-inline int resident_waves(int api_answer) {
-  int cap = 24;
-  if (const char *s = std::getenv("GTOK_MAX_WAVES_PER_CU")) {
-    const int c = std::atoi(s);
-    if (c >= 1) cap = c;
-  }
-  return api_answer < cap ? api_answer : cap;
-}
+inline int resident_waves(int api_answer) { return capped(api_answer, "GTOK_MAX_WAVES_PER_CU", 24); }
 
 __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -288,7 +280,7 @@ struct LaunchMemo {
   int nr = 0;
 };
 inline LaunchMemo &launch_memo() { static LaunchMemo m; return m; }
-// hipOccupancyMaxActiveBlocksPerMultiprocessor, remembered per (kernel, device, block size, LDS bytes); 0 = the query failed
+// hipOccupancyMaxActiveBlocksPerMultiprocessor, remembered per (kernel, device, block size, LDS bytes); 0 = the query failed.  (64 entries shared by every launcher: what a process meets beyond them is asked of the runtime on every call)
 inline int occupancy_of(const void *kern, int dev, int block, size_t lds) {
   LaunchMemo &m = launch_memo();
   {
@@ -314,6 +306,57 @@ inline bool raise_lds_limit(const void *kern, int dev) {
   std::lock_guard<std::mutex> lock(m.mu);
   if (m.nr < 64) { m.raised[m.nr] = kern; m.raised_dev[m.nr] = dev; ++m.nr; }
   return true;
+}
+
+// ---- launch planning shared by the launchers
+inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
+
+// f(std::true_type) or f(std::false_type): a runtime flag as a template argument
+template <class F> auto with_flag(bool b, F f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+
+// Waves per workgroup of a kernel whose waves each own `stride` bytes of dynamic LDS (and that has no static LDS): `start`, halved
+// until the workgroup fits 64 KB.  One wave that still needs more takes the opt-in (callers refuse a stride above 160 KB first).
+// 0: the opt-in failed.
+inline int waves_per_block(const void *kern, int dev, int start, int stride) {
+  int wpb = start;
+  while (wpb > 1 && wpb * stride > 64 * 1024) wpb >>= 1;
+  if (wpb * stride > 64 * 1024 && !raise_lds_limit(kern, dev)) return 0;
+  return wpb;
+}
+
+// One-round grid over `items` work items, `wpb` of them to a unit (one per wave of a workgroup): CUs x resident workgroups per CU,
+// at most one per unit; a workgroup walks `upb` consecutive units and the grid is evened out over that - except where the waves
+// draw their units from tickets (Waves, Tickets: upb is not used).  Workgroups per CU, from the runtime's answer: Blocks =
+// resident_blocks() (the wave-per-item kernels), Cap32 = at most 32 (ibtt_zinc_quad_kernel), Waves = resident_waves() (sent_lds_kernel's
+// one-wave workgroups), Tickets = as answered (ibtt_zinc_lane_kernel).
+enum class Resident { Blocks, Cap32, Waves, Tickets };
+struct Grid { int units, upb, nb; };
+inline Grid plan_grid(const void *kern, int dev, int items, int wpb, size_t lds, Resident cap) {
+  int occ = occupancy_of(kern, dev, wpb * 64, lds);
+  if (occ < 1) occ = 1;
+  if (cap == Resident::Blocks) occ = resident_blocks(occ);
+  if (cap == Resident::Cap32 && occ > 32) occ = 32;
+  if (cap == Resident::Waves) occ = resident_waves(occ);
+  Grid G;
+  G.units = (items + wpb - 1) / wpb;
+  G.nb = device_cu_count(dev) * occ;
+  if (G.nb > G.units) G.nb = G.units;
+  G.upb = (G.units + G.nb - 1) / G.nb;
+  if (cap == Resident::Blocks || cap == Resident::Cap32) G.nb = (G.units + G.upb - 1) / G.upb;
+  return G;
+}
+
+// Launch of a wave-per-item kernel (Args by value, carrying units / upb) whose waves each own `stride` bytes of dynamic LDS
+template <class Args>
+int launch_wave_per_item(void (*kern)(const Args), Args &a, int items, int start_wpb, int stride, int dev, hipStream_t stream) {
+  const void *k = reinterpret_cast<const void *>(kern);
+  const int wpb = waves_per_block(k, dev, start_wpb, stride);
+  if (!wpb) return GTOK_E_LAUNCH;
+  const size_t lds = (size_t)wpb * stride;
+  const Grid G = plan_grid(k, dev, items, wpb, lds, Resident::Blocks);
+  a.units = G.units; a.upb = G.upb;
+  hipLaunchKernelGGL(kern, dim3(G.nb), dim3(wpb * 64), lds, stream, a);
+  return hipGetLastError() == hipSuccess ? GTOK_OK : GTOK_E_LAUNCH;
 }
 
 __device__ __forceinline__ uint32_t uni(uint32_t v) {

@@ -750,6 +750,70 @@ static int tpr_shift_for(int ld) {
   return s;
 }
 
+// ---------------------------------------------------------------------------------------------
+// remap_zinc_tokens over a slab; batch collate
+// ---------------------------------------------------------------------------------------------
+__global__ void remap_kernel(const int32_t *__restrict__ in, int32_t *__restrict__ out, int ld,
+                             const int32_t *__restrict__ len, int rows, int idx_off, int node_off,
+                             int edge_off) {
+  const int64_t total = (int64_t)rows * ld;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int r = (int)(i / ld), c = (int)(i - (int64_t)r * ld);
+    const int t = in[i];
+    out[i] = c < len[r] ? remap_zinc_token(t, idx_off, node_off, edge_off) : t;
+  }
+}
+
+__global__ void batch_max_kernel(const int32_t *__restrict__ len, const int64_t *__restrict__ index,
+                                 int batch, int32_t *__restrict__ batch_max) {
+  __shared__ int red[4];
+  int m = 0;
+  for (int b = threadIdx.x; b < batch; b += blockDim.x) m = max(m, len[index[b]]);
+  for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_down(m, o));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) m = max(m, red[w]);
+    batch_max[0] = m;
+  }
+}
+
+// one wave per batch row: int32 slab row -> int64 ids + bool mask
+__global__ void __launch_bounds__(256) collate_kernel(const int32_t *__restrict__ ids, int ld,
+                                                      const int32_t *__restrict__ len,
+                                                      const int64_t *__restrict__ index, int batch,
+                                                      int pad_id, int64_t *__restrict__ out_x,
+                                                      uint8_t *__restrict__ out_attn, int out_ld) {
+  const int lane = lane_id();
+  const int b = (int)blockIdx.x * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6);
+  if (b >= batch) return;
+  const int64_t src = index[b];
+  const int l = len[src];
+  const int32_t *__restrict__ row = ids + src * (int64_t)ld;
+  for (int i = lane; i < out_ld; i += kWave) {
+    const bool in = i < l && i < ld;
+    out_x[(int64_t)b * out_ld + i] = in ? (int64_t)row[i] : (int64_t)pad_id;
+    out_attn[(int64_t)b * out_ld + i] = in ? 1 : 0;
+  }
+}
+
+// one wave per row: first column holding `token` (ballot + ffs over 64-column chunks), -1 if none
+__global__ void __launch_bounds__(256) find_token_kernel(const int64_t *__restrict__ x, int rows, int ld, int64_t token,
+                                                         int32_t *__restrict__ pos) {
+  const int lane = lane_id();
+  const int r = (int)blockIdx.x * (int)(blockDim.x >> 6) + wave_id();
+  if (r >= rows) return;
+  const int64_t *__restrict__ row = x + (int64_t)r * ld;
+  int found = -1;
+  for (int c0 = 0; c0 < ld; c0 += kWave) {
+    const int i = c0 + lane;
+    const uint64_t hit = __ballot(i < ld && row[i] == token);
+    if (hit) { found = c0 + __builtin_ctzll(hit); break; }
+  }
+  if (lane == 0) pos[r] = found;
+}
+
 }  // namespace gtok
 
 using namespace gtok;
@@ -1040,5 +1104,47 @@ extern "C" int gtok_zinc_text_tails(const float *y, const int32_t *len, int64_t 
   TailArgs a;
   a.y = y; a.len = len; a.rows = num_rows; a.max_len = max_len; a.take = take; a.suf_ptr = suf_ptr; a.out = suf_bytes; a.suf_len = suf_len;
   hipLaunchKernelGGL(zinc_text_tails_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, a);
+  return hipGetLastError() == hipSuccess ? GTOK_OK : GTOK_E_LAUNCH;
+}
+
+extern "C" int gtok_remap_zinc(const int32_t *in_ids, int32_t *out_ids, int32_t ld, const int32_t *len,
+                               int32_t num_rows, int32_t idx_offset, int32_t node_idx_offset,
+                               int32_t edge_idx_offset, void *stream) {
+  gtok::DeviceScope device_scope((hipStream_t)stream);   // the stream's device, not the thread's current one
+  if (!device_scope.ok()) return GTOK_E_NO_DEVICE;
+  if (!in_ids || !out_ids || !len || ld <= 0 || num_rows < 0) return GTOK_E_INVAL;
+  if (num_rows == 0) return GTOK_OK;
+  const int64_t total = (int64_t)num_rows * ld;
+  int nb = (int)((total + 255) / 256);
+  if (nb > 256 * 8) nb = 256 * 8;
+  hipLaunchKernelGGL(remap_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, in_ids, out_ids, ld, len,
+                     num_rows, idx_offset, node_idx_offset, edge_idx_offset);
+  return hipGetLastError() == hipSuccess ? GTOK_OK : GTOK_E_LAUNCH;
+}
+
+extern "C" int gtok_collate(const int32_t *ids, int32_t ld, const int32_t *len, const int64_t *index,
+                            int32_t batch, int32_t pad_id, int64_t *out_x, uint8_t *out_attn,
+                            int32_t out_ld, int32_t *batch_max, void *stream) {
+  gtok::DeviceScope device_scope((hipStream_t)stream);   // the stream's device, not the thread's current one
+  if (!device_scope.ok()) return GTOK_E_NO_DEVICE;
+  if (!ids || !len || !index || ld <= 0 || batch < 0 || out_ld < 0) return GTOK_E_INVAL;
+  if (batch == 0) return GTOK_OK;
+  if (batch_max)
+    hipLaunchKernelGGL(batch_max_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, len, index, batch, batch_max);
+  if (out_ld > 0) {
+    if (!out_x || !out_attn) return GTOK_E_INVAL;
+    hipLaunchKernelGGL(collate_kernel, dim3((batch + 3) / 4), dim3(256), 0, (hipStream_t)stream, ids, ld, len,
+                       index, batch, pad_id, out_x, out_attn, out_ld);
+  }
+  return hipGetLastError() == hipSuccess ? GTOK_OK : GTOK_E_LAUNCH;
+}
+
+extern "C" int gtok_find_token(const int64_t *x, int32_t rows, int32_t ld, int64_t token, int32_t *pos, void *stream) {
+  gtok::DeviceScope device_scope((hipStream_t)stream);   // the stream's device, not the thread's current one
+  if (!device_scope.ok()) return GTOK_E_NO_DEVICE;
+  if (rows < 0 || ld < 0) return GTOK_E_INVAL;
+  if (rows == 0) return GTOK_OK;
+  if (!pos || (ld > 0 && !x)) return GTOK_E_INVAL;
+  hipLaunchKernelGGL(find_token_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, rows, ld, token, pos);
   return hipGetLastError() == hipSuccess ? GTOK_OK : GTOK_E_LAUNCH;
 }

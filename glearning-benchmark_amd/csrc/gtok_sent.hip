@@ -16,7 +16,6 @@
 // This file is the launcher: argument checks, kernel choice, and per kernel the LDS layout, instantiation and grid sizing.
 #include <cstdio>
 #include <cstdlib>
-#include <type_traits>
 
 #include "gtok_common.hpp"
 #include "gtok.h"
@@ -34,7 +33,6 @@ constexpr int GTOK_LANE_MIN_GRAPHS = 28000;     // measured crossover on ZINC-sh
 // 4 k to 16 k graphs of 10-256 nodes, profiles/tools/blane_crossover.sh: ER crosses at ~24 k, the family mix at ~11 k)
 constexpr int GTOK_BLANE_MIN_GRAPHS = 20000;
 
-static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 static inline int sent_epochs(const gtok_sent_params *p) { return p->epoch_count > 1 ? p->epoch_count : 1; }
 static inline int sent_maxn(const gtok_csr *g) { return g->max_nodes > 0 ? g->max_nodes : 1; }
 // 64-bit words of an adjacency row (sent_lds_kernel's W; the mirror of sent_blane_kernel stops at 4)
@@ -89,9 +87,6 @@ struct SentCall {
   bool u16, pk8;           // GTOK_SENT_U16, GTOK_SENT_PACK_U8
   int pad_nt;              // pad with non-temporal stores (the lane-per-graph kernels)
 };
-
-// f(std::true_type) or f(std::false_type): a runtime flag as a template argument
-template <class F> auto with_flag(bool b, F f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
 
 // Every test gtok_sent makes before a launcher fills its argument struct, in the order that decides which error an input
 // with two faults gets; fills the derived fields of `c` (which == None behind GTOK_OK: an empty batch, nothing to launch).
@@ -274,13 +269,6 @@ int launch_lane(const SentCall &c) {
   const LaneKernel kern = !p->labeled ? lane_kernel<0>(p3, pk, c.u16, pack, c.pk8)
                           : p->remap_zinc ? lane_kernel<2>(p3, pk, c.u16, pack, c.pk8) : lane_kernel<1>(p3, pk, c.u16, pack, c.pk8);
   const int ncu = device_cu_count(c.dev);
-  int occ = -1;                                 // occupancy of one-wave workgroups: only the fallback launch below asks
-  if (const char *cs = std::getenv("GTOK_LANE_BLOCKS_PER_CU")) {   // tuning knob
-    occ = occupancy_of(reinterpret_cast<const void *>(kern), c.dev, 64, (size_t)a.lds);
-    if (occ < 1) occ = 1;
-    const int n = std::atoi(cs);
-    if (n >= 1 && n < occ) occ = n;
-  }
   a.units = g->unit_ptr ? g->num_units : (g->num_graphs + 63) / 64; a.epochs = K; a.pad_nt = c.pad_nt;
   if ((int64_t)a.units * K > 0x7FFFFFFF / 64) return GTOK_E_TOO_LARGE;
   const int vunits = a.units * K;               // (unit, epoch) pairs the launch walks
@@ -302,10 +290,9 @@ int launch_lane(const SentCall &c) {
     while (gcd(m, vunits) != 1) ++m;
     a.unit_mul = m;
   }
-  if (occ < 0) {
-    occ = occupancy_of(reinterpret_cast<const void *>(kern), c.dev, 64, (size_t)a.lds);
-    if (occ < 1) occ = 1;
-  }
+  int occ = occupancy_of(reinterpret_cast<const void *>(kern), c.dev, 64, (size_t)a.lds);   // one-wave workgroups
+  if (occ < 1) occ = 1;
+  if (const char *cs = std::getenv("GTOK_LANE_BLOCKS_PER_CU")) { const int n = std::atoi(cs); if (n >= 1 && n < occ) occ = n; }   // tuning knob
   int nb = ncu * occ;
   if (nb > vunits) nb = vunits;
   if (a.pack_scratch && nb > ncu * 16) nb = ncu * 16;     // (the staging space is 64 rows for each of 16 waves per CU)
@@ -354,11 +341,6 @@ int launch_wave(const SentCall &c) {
   }
   a.l.stride = align_up(off, 16);
   if (a.l.stride > 160 * 1024) return GTOK_E_TOO_LARGE;
-  // sent_lds_kernel waves never cooperate and draw graphs from a queue: one wave per workgroup packs LDS best
-  int wpb = reg_path ? 4 : 1;
-  while (wpb > 1 && wpb * a.l.stride > 64 * 1024) wpb >>= 1;
-  const size_t lds = (size_t)wpb * a.l.stride;
-
   WaveKernel kern;
   if (reg_path) {
     // no truncation test in the walk when max_len can hold the longest possible trail of this batch
@@ -368,30 +350,21 @@ int launch_wave(const SentCall &c) {
   } else {
     kern = W == 1 ? lds_kernel<1>(p->labeled) : W == 2 ? lds_kernel<2>(p->labeled) : W == 4 ? lds_kernel<4>(p->labeled) : lds_kernel<8>(p->labeled);
   }
-  if (lds > 64 * 1024 && !raise_lds_limit(reinterpret_cast<const void *>(kern), c.dev)) return GTOK_E_LAUNCH;
-  const int ncu = device_cu_count(c.dev);
-  int occ = occupancy_of(reinterpret_cast<const void *>(kern), c.dev, wpb * 64, lds);
-  if (occ < 1) occ = 1;
+  // sent_lds_kernel waves never cooperate and draw graphs from a queue: one wave per workgroup packs LDS best
+  const int wpb = waves_per_block(reinterpret_cast<const void *>(kern), c.dev, reg_path ? 4 : 1, a.l.stride);
+  if (!wpb) return GTOK_E_LAUNCH;
+  const size_t lds = (size_t)wpb * a.l.stride;
+  // sent_reg_kernel: upb consecutive units per workgroup; sent_lds_kernel: one-wave workgroups that draw the pairs from tickets
+  const Grid G = plan_grid(reinterpret_cast<const void *>(kern), c.dev, pairs, wpb, lds, reg_path ? Resident::Blocks : Resident::Waves);
+  a.units = G.units; a.upb = reg_path ? G.upb : 0;
   a.queue = nullptr;
   QueueSlot slot;
-  int nb;
-  if (reg_path) {
-    occ = gtok::resident_blocks(occ);
-    a.units = (pairs + wpb - 1) / wpb;
-    nb = ncu * occ;
-    if (nb > a.units) nb = a.units;
-    a.upb = (a.units + nb - 1) / nb;
-    nb = (a.units + a.upb - 1) / a.upb;
-  } else {
-    occ = gtok::resident_waves(occ);     // one-wave workgroups
-    a.units = pairs; a.upb = 0;
-    nb = ncu * occ;
-    if (nb > a.units) nb = a.units;
+  if (!reg_path) {
     slot = take_queue_slot(c.dev, c.stream);
     a.queue = slot.counters;
     if (!a.queue) return slot.graph_pool_empty ? GTOK_E_GRAPH_SLOTS : GTOK_E_LAUNCH;
   }
-  hipLaunchKernelGGL(kern, dim3(nb), dim3(wpb * 64), lds, c.stream, a);
+  hipLaunchKernelGGL(kern, dim3(G.nb), dim3(wpb * 64), lds, c.stream, a);
   mark_queue_slot(slot, c.stream);
   return hipGetLastError() == hipSuccess ? GTOK_OK : GTOK_E_LAUNCH;
 }

@@ -10,7 +10,7 @@ if [ "$1" = build ]; then
   mkdir -p $ab
   for v in $variants; do
     ( tmp=$(mktemp -d)
-      for f in gtok_sent gtok_ibtt gtok_rows; do
+      for f in gtok_sent gtok_sent_large gtok_ibtt gtok_text gtok_rows gtok_csr; do
         obj=$root/glearning-benchmark_amd/csrc/_obj/$f.hip.o
         if [ $f = gtok_sent ]; then
           /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -c -DGTOK_ABLATE_$v -I$root/include -o $tmp/$f.o $root/glearning-benchmark_amd/csrc/$f.hip

@@ -4,7 +4,7 @@ hold s_memtime sums for node selection / row load + counters + position token / 
 tokens / row end + padding, the wave-level step and bracket-iteration counts, and the unit's life on the 100 MHz
 clock).  Never ship that build.
     hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -shared -DGTOK_PHASE_TIMING -Iinclude \
-        -o glearning-benchmark_amd/csrc/libgtok_prof.so glearning-benchmark_amd/csrc/gtok_sent.hip glearning-benchmark_amd/csrc/gtok_ibtt.hip
+        -o glearning-benchmark_amd/csrc/libgtok_prof.so glearning-benchmark_amd/csrc/*.hip
     GTOK_LIB=glearning-benchmark_amd/csrc/libgtok_prof.so python profiles/tools/phase_timing_blane.py"""
 import importlib, os, sys
 import numpy as np, torch

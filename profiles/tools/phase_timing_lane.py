@@ -3,7 +3,7 @@
 s_memtime deltas for staging / counter init / walk / row end, the wave's start and end on the 100 MHz real-time
 clock, the walk's iteration count and the workgroup id).  Never ship that build.
     hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -shared -DGTOK_PHASE_TIMING -Iinclude \
-        -o glearning-benchmark_amd/csrc/libgtok_prof.so glearning-benchmark_amd/csrc/gtok_sent.hip glearning-benchmark_amd/csrc/gtok_ibtt.hip
+        -o glearning-benchmark_amd/csrc/libgtok_prof.so glearning-benchmark_amd/csrc/*.hip
     GTOK_LIB=glearning-benchmark_amd/csrc/libgtok_prof.so python profiles/tools/phase_timing_lane.py"""
 import importlib, os, sys
 import numpy as np, torch

@@ -1,6 +1,7 @@
 """GPU parity: every HIP entry point, called through the C ABI, against the CPU oracle — bit-exact
 (integer work).  Sizes are what the oracle finishes in seconds; corpus-scale properties live in
 test_gpu_properties.py."""
+import ctypes
 import os
 import numpy as np
 import pytest
@@ -1181,3 +1182,62 @@ def test_graph_token_text_parser_streamed_edge_zone_against_the_host_parser():
     for g, text in enumerate(texts):
         edges, n, label = gm.parse_graph_from_json({"text": text})
         assert got[g] == (edges, n, label, gm.parse_query_nodes_from_text(text)), (g, int(st[g]), text[:80])
+
+
+LDS_OPT_IN = (64 * 1024, 160 * 1024)      # a wave's dynamic LDS above the first needs the opt-in; the launchers refuse more than the second
+
+
+def test_ibtt_zinc_wave_kernel_with_more_than_64_kb_of_lds(monkeypatch):
+    """ibtt_zinc_kernel with one wave per workgroup and a slice above 64 KB: the launch that needs the dynamic-LDS opt-in.  The
+    slice, as the launcher lays it out, is 4 (n + 1) + 9 E + 4 tcap bytes (+ alignment), tcap = 6 + 2 n + 4 E under max_len and ld."""
+    monkeypatch.setenv("GTOK_IBTT_KERNEL", "wave")
+    d = _symmetric_er(24, 11, 60, 100, 0.3, 0.5)
+    batch, coo = both(d)
+    max_len = 32768
+    n, E = batch.max_nodes, batch.max_edges
+    vocab = zinc_vocab(128)
+    lut = gtok.ops.zinc_lut(vocab, 128)
+    assert batch.flags & 1 and batch.eorder is None and n <= 128
+    ids, ln = gtok.ops.ibtt_zinc(batch.to(DEV), lut, max_len, vocab["<pad>"])
+    stride = 4 * (n + 1) + 9 * E + 4 * min(6 + 2 * n + 4 * E, max_len, ids.shape[1])
+    assert LDS_OPT_IN[0] < stride <= LDS_OPT_IN[1], (n, E, stride)
+    ref, rln = orc.ibtt_zinc(coo, lut.numpy(), max_len, vocab["<pad>"], ids.shape[1])
+    _cmp(ids, ln, ref, rln, f"ibtt_zinc wave, {stride} bytes of LDS per wave")
+
+
+def test_ibtt_synth_kernel_with_more_than_64_kb_of_lds():
+    """The same for ibtt_synth_kernel: 4 (n + 1) + 4 tcap + 4 lut_len bytes (+ alignment), tcap = 3 E + n + 7 under max_len and ld."""
+    d = gtok.synth.er_batch(16, seed=12, min_nodes=100, max_nodes=150, min_sparsity=0.5, max_sparsity=0.8)
+    batch, coo = both(d, False)
+    max_len = 100000
+    n, E = batch.max_nodes, batch.max_edges
+    vocab = {t: i for i, t in enumerate(["<pad>", "<bos>", "<e>", "<n>", "<q>", "<p>", "<eos>", "yes", "no", "has_cycle"] + [str(i) for i in range(160)])}
+    lut = gtok.ops.synth_lut(vocab, 160)
+    assert n <= 160
+    q = np.zeros((batch.num_graphs, 4), np.int32); q[:, 0] = 1; q[:, 1] = vocab["has_cycle"]
+    ids, ln = gtok.ops.ibtt_synth(batch.to(DEV), lut, torch.from_numpy(q), max_len, 0)
+    stride = 4 * (n + 1) + 4 * min(3 * E + n + 7, max_len, ids.shape[1]) + 4 * lut.numel()
+    assert LDS_OPT_IN[0] < stride <= LDS_OPT_IN[1], (n, E, stride)
+    ref, rln = orc.ibtt_synth(coo, lut.numpy(), q, max_len, 0, ids.shape[1])
+    _cmp(ids, ln, ref, rln, f"ibtt_synth, {stride} bytes of LDS per wave")
+
+
+@pytest.mark.parametrize("group", ["8", "16"])
+@pytest.mark.parametrize("ld", [64, 67])
+def test_ibtt_zinc_quad_kernel_with_the_group_size_pinned(group, ld, monkeypatch):
+    """GTOK_IBTT_GROUP pins 8 or 16 lanes per molecule in ibtt_zinc_quad_kernel, on molecules the 8-lane pipeline covers; ld 64: the
+    unit's rows are assembled in LDS, ld 67: they are not."""
+    monkeypatch.setenv("GTOK_IBTT_KERNEL", "quad")
+    monkeypatch.setenv("GTOK_IBTT_GROUP", group)
+    d = gtok.synth.zinc_like(500, seed=92)
+    batch, coo = both(d)
+    assert batch.flags & 1 and batch.eorder is None and batch.max_nodes <= 48 and batch.max_edges <= 96
+    vocab = zinc_vocab(40)
+    lut = gtok.ops.zinc_lut(vocab, 40)
+    b = batch.to(DEV)
+    cs = b.c_struct()
+    assert gtok.lib().gtok_ibtt_zinc_kernel_name(ctypes.byref(cs)).decode() == "ibtt_zinc_quad_kernel"
+    for max_len in (1024, 64, 10):
+        ids, ln = gtok.ops.ibtt_zinc(b, lut, max_len, vocab["<pad>"], ld=ld)
+        ref, rln = orc.ibtt_zinc(coo, lut.numpy(), max_len, vocab["<pad>"], ld)
+        _cmp(ids, ln, ref, rln, f"ibtt_zinc quad group={group} ld={ld} max_len={max_len}")
