@@ -101,6 +101,35 @@ class Graph2TrailTokenizer:
                          remap_zinc=remap_zinc, pad_id=self.pad, graph_base=graph_base, query=query, ld=ld, out=out, pad=pad,
                          epochs=epochs, u16=u16)
 
+    # ---- the way back: sequences -> graphs
+    def decode_batch(self, ids: torch.Tensor, ln: torch.Tensor, row_start: Optional[torch.Tensor] = None, check_symmetric: bool = False):
+        """Un-remapped rows (tokenize_batch's slabs, int32 or 16-bit, or packed rows with row_start) -> (GraphBatch, status int32
+        [rows]) on the device: ops.sent_decode_csr with this tokenizer's max_num_nodes, labeled_graph and num_node_types.  Graph r is
+        row r in visit-index space; status 0 complete, 1 malformed (an empty graph), 3 cut before EOS."""
+        if self.max_num_nodes is None:
+            raise RuntimeError("call set_num_nodes() first")
+        return _ops.sent_decode_csr(ids, ln, self.max_num_nodes, labeled=self.labeled_graph, num_node_types=self.num_node_types,
+                                    row_start=row_start, check_symmetric=check_symmetric)
+
+    def decode(self, tokens) -> dict:
+        """One sequence (a 1-D tensor of un-remapped ids, as tokenizer(data) returns them) -> dict(num_nodes, edge_index int64 [2, E]
+        with both directions of every edge in stream order, x int64 [num_nodes] and edge_attr int64 [E] (None when unlabelled; 255 =
+        no type), status) on the host."""
+        t = torch.as_tensor(tokens).reshape(1, -1).to(self._device(), dtype=torch.int32).contiguous()
+        if t.shape[1] == 0:
+            t = torch.full((1, 1), self.pad, dtype=torch.int32, device=t.device)
+            ln = torch.zeros(1, dtype=torch.int32, device=t.device)
+        else:
+            ln = torch.full((1,), t.shape[1], dtype=torch.int32, device=t.device)
+        b, status = self.decode_batch(t, ln)
+        n, e = int(b.node_ptr[1]), int(b.edge_ptr[1])
+        counts = (b.rowptr[1:n + 1] - b.rowptr[:n]).to(torch.int64)
+        src = torch.repeat_interleave(torch.arange(n, device=t.device), counts, output_size=e)
+        order = torch.arange(e, device=t.device) if b.eorder is None else torch.argsort(b.eorder.to(torch.int64))
+        edge_index = torch.stack([src, b.col.to(torch.int64)])[:, order]
+        long = lambda a, o=None: None if a is None else (a if o is None else a[o]).to(torch.int64).cpu()
+        return dict(num_nodes=n, edge_index=edge_index.cpu(), x=long(b.nattr), edge_attr=long(b.eattr, order), status=int(status[0]))
+
     EPOCH_WALKS = 1 << 22         # walks per launch: sixteen rounds of the 4,096 resident waves x 64 lanes of sent_lane_kernel - units that
                                   # are staged and padded while other waves walk cost less than those of a one-round launch, and the
                                   # launch's ragged end is shared by more epochs (ZINC-full as 16-bit rows, per epoch: 0.0653 ms at one

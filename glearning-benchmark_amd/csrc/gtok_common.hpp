@@ -317,10 +317,11 @@ template <class F> auto with_flag(bool b, F f) { return b ? f(std::true_type{}) 
 // Waves per workgroup of a kernel whose waves each own `stride` bytes of dynamic LDS (and that has no static LDS): `start`, halved
 // until the workgroup fits 64 KB.  One wave that still needs more takes the opt-in (callers refuse a stride above 160 KB first).
 // 0: the opt-in failed.
+constexpr int kLdsWithoutOptIn = 64 * 1024;   // dynamic LDS a workgroup gets without hipFuncAttributeMaxDynamicSharedMemorySize
 inline int waves_per_block(const void *kern, int dev, int start, int stride) {
   int wpb = start;
-  while (wpb > 1 && wpb * stride > 64 * 1024) wpb >>= 1;
-  if (wpb * stride > 64 * 1024 && !raise_lds_limit(kern, dev)) return 0;
+  while (wpb > 1 && wpb * stride > kLdsWithoutOptIn) wpb >>= 1;
+  if (wpb * stride > kLdsWithoutOptIn && !raise_lds_limit(kern, dev)) return 0;
   return wpb;
 }
 

@@ -772,6 +772,111 @@ def sent_decode(ids: torch.Tensor, ln: torch.Tensor, max_num_nodes: int, labeled
     return out
 
 
+def _decode_rows(ids: torch.Tensor, ln: torch.Tensor, row_start: Optional[torch.Tensor], ld: Optional[int], what: str):
+    """The row arguments of gtok_sent_decode_sizes / gtok_sent_decode_csr, checked: -> (elem_bytes, ld, rows)."""
+    _need_gpu(ids, what)
+    if ln.dtype != torch.int32 or ln.dim() != 1 or not ln.is_contiguous() or ln.device != ids.device:
+        raise ValueError(f"{what}: lengths must be a contiguous int32 vector on the rows' device")
+    rows = int(ln.numel())
+    if not ids.is_contiguous():
+        raise ValueError(f"{what}: ids must be contiguous")
+    if row_start is None:
+        if ids.dtype not in (torch.int32, torch.int16) or ids.dim() != 2 or int(ids.shape[0]) != rows:
+            raise ValueError(f"{what}: without row_start, ids is an int32 or int16 [rows, ld] slab with one length per row")
+        if ld is not None and int(ld) != int(ids.shape[1]):
+            raise ValueError(f"{what}: ld is the slab's width")
+        ld = int(ids.shape[1])
+    else:
+        if ids.dtype not in (torch.uint8, torch.int16, torch.int32) or ids.dim() != 1:
+            raise ValueError(f"{what}: with row_start, ids is a flat uint8 / int16 / int32 buffer of packed rows")
+        if row_start.dtype != torch.int64 or row_start.dim() != 1 or not row_start.is_contiguous() or int(row_start.numel()) < rows \
+                or row_start.device != ids.device:
+            raise ValueError(f"{what}: row_start must be a contiguous int64 vector of (at least) one start per row on the rows' device")
+        ld = 0x7FFFFFFF if ld is None else int(ld)           # (a packed row holds min(len, ld) ids: by default all of its len)
+    return ids.element_size(), ld, rows
+
+
+def _need_decode_csr() -> None:
+    """The two entry points came without an ABI version step: a library loaded through GTOK_LIB may lack them."""
+    if not all(hasattr(lib(), n) for n in _lib.DECODE_CSR_SYMBOLS):
+        raise _lib.GtokError(f"{_lib.LIB_PATH} has no gtok_sent_decode_sizes / gtok_sent_decode_csr: it was built before they were added")
+
+
+def sent_decode_sizes(ids: torch.Tensor, ln: torch.Tensor, max_num_nodes: int, labeled: bool = False, num_node_types: int = 0,
+                      row_start: Optional[torch.Tensor] = None, ld: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """gtok_sent_decode_sizes: (num_nodes, num_entries, status) int32 [rows] of un-remapped SENT rows - the sizes of the graphs
+    sent_decode_csr builds (a status-1 row: 0, 0).  ids / row_start / ld as there.  Nothing is read back."""
+    eb, ld, rows = _decode_rows(ids, ln, row_start, ld, "sent_decode_sizes")
+    _need_decode_csr()
+    dev = ids.device
+    nn, ne, st = (torch.empty(rows, dtype=torch.int32, device=dev) for _ in range(3))
+    if rows:
+        check(lib().gtok_sent_decode_sizes(ids.data_ptr(), eb, None if row_start is None else row_start.data_ptr(), ld, ln.data_ptr(), rows,
+                                           int(max_num_nodes), int(bool(labeled)), int(num_node_types), nn.data_ptr(), ne.data_ptr(),
+                                           st.data_ptr(), _stream(dev)), "gtok_sent_decode_sizes")
+    return nn, ne, st
+
+
+def _decode_csr_launch(ids, ln, row_start, ld, max_num_nodes, labeled, num_node_types, node_ptr, edge_ptr, N: int, E: int) -> dict:
+    """gtok_sent_decode_csr on the current stream into fresh arrays of the given totals: -> dict of gtok_csr_built's arrays
+    (nattr / eattr None when unlabelled); no host read."""
+    eb, ld, rows = _decode_rows(ids, ln, row_start, ld, "sent_decode_csr")
+    _need_decode_csr()
+    dev = ids.device
+    if node_ptr.dtype != torch.int32 or edge_ptr.dtype != torch.int64 or node_ptr.numel() != rows + 1 or edge_ptr.numel() != rows + 1 \
+            or not node_ptr.is_contiguous() or not edge_ptr.is_contiguous() or node_ptr.device != dev or edge_ptr.device != dev:
+        raise ValueError("sent_decode_csr: node_ptr int32 [rows + 1] and edge_ptr int64 [rows + 1] on the rows' device")
+    N, E = int(N), int(E)
+    if N < 0 or E < 0 or N + rows >= 2 ** 31:
+        raise ValueError("sent_decode_csr: totals out of range (a batch holds fewer than 2^31 nodes + graphs; shard it)")
+    # (the library wants an address for every array, and an empty tensor has none: one spare element, sliced off)
+    new = lambda n, dt: torch.empty(n + 1, dtype=dt, device=dev)
+    full = dict(node_ptr=node_ptr, edge_ptr=edge_ptr, rowptr=new(N + rows, torch.int32), col=new(E, torch.int32), eorder=new(E, torch.int32),
+                nattr=new(N, torch.uint8) if labeled else None, eattr=new(E, torch.uint8) if labeled else None, info=new(8, torch.int32))
+    o = {k: t if t is None or k in ("node_ptr", "edge_ptr") else t[:-1] for k, t in full.items()}
+    if rows == 0:
+        o["info"].zero_()
+        return o
+    ptr = lambda t: None if t is None else t.data_ptr()
+    cout = _lib.GtokCsrBuilt(*[ptr(full[n]) for n, _ in _lib.GtokCsrBuilt._fields_])
+    check(lib().gtok_sent_decode_csr(ids.data_ptr(), eb, ptr(row_start), ld, ln.data_ptr(), rows, int(max_num_nodes), int(bool(labeled)),
+                                     int(num_node_types), ctypes.byref(cout), _stream(dev)), "gtok_sent_decode_csr")
+    return o
+
+
+def sent_decode_csr(ids: torch.Tensor, ln: torch.Tensor, max_num_nodes: int, labeled: bool = False, num_node_types: int = 0,
+                    row_start: Optional[torch.Tensor] = None, check_symmetric: bool = False,
+                    ld: Optional[int] = None) -> Tuple[GraphBatch, torch.Tensor]:
+    """Un-remapped SENT rows -> (GraphBatch on the rows' device, status int32 [rows]): row r becomes graph r in visit-index
+    space (node k = the k-th node the trail visited), every decoded edge listed in both directions, the arrays those of
+    GraphBatch.from_coo over that list (include/gtok.h: gtok_sent_decode_sizes / gtok_sent_decode_csr).  status: 0 complete,
+    1 malformed (an empty graph), 3 cut before EOS (the part that was read).
+    ids: an int32 or int16 (16-bit ids) [rows, ld] slab, or - with row_start int64 [rows] - a flat uint8 / int16 / int32 buffer
+    of packed rows (PackedRows.buf / .row_start, pack_rows_scan's packed / row_ptr; a negative start = an empty row; ld = the
+    slab width the rows were cut at, when some len exceeds it).  Every row must lie inside `ids`: that is not checked.
+    Two read-backs: the two totals after the sizing pass, `info` after the build.  check_symmetric: gtok_csr_check over the
+    result sets CSR_SIMPLE_SYMMETRIC when every graph is simple (a third read-back); a batch without a single entry is left
+    unflagged and unchecked, as GraphBatch.from_coo leaves it."""
+    nn, ne, status = sent_decode_sizes(ids, ln, max_num_nodes, labeled, num_node_types, row_start, ld)
+    dev, rows = ids.device, int(ln.numel())
+    node_ptr64 = torch.zeros(rows + 1, dtype=torch.int64, device=dev); torch.cumsum(nn, 0, dtype=torch.int64, out=node_ptr64[1:])
+    edge_ptr = torch.zeros(rows + 1, dtype=torch.int64, device=dev); torch.cumsum(ne, 0, dtype=torch.int64, out=edge_ptr[1:])
+    N, E = torch.stack([node_ptr64[-1], edge_ptr[-1]]).tolist()            # the read-back of the two totals
+    if N + rows >= 2 ** 31:
+        raise ValueError("batch too large for int32 node offsets; shard it")
+    o = _decode_csr_launch(ids, ln, row_start, ld, max_num_nodes, labeled, num_node_types, node_ptr64.to(torch.int32), edge_ptr, N, E)
+    v = o["info"].tolist()                                                  # ... and of info
+    if v[0]:
+        raise _lib.GtokError(f"sent_decode_csr: {v[0]} rows changed between the two passes")
+    b = GraphBatch(rows, v[2], v[3], o["node_ptr"], o["edge_ptr"], o["rowptr"], o["col"], o["eorder"] if v[7] else None, o["nattr"], o["eattr"],
+                   0, v[4], v[5], v[1] if N else 0)
+    if check_symmetric and E:
+        if csr_check(b)["violations"] == 0:
+            b.flags |= _lib.CSR_SIMPLE_SYMMETRIC
+        b.checked = True
+    return b, status
+
+
 def remap_zinc(ids: torch.Tensor, ln: torch.Tensor, idx_offset: int, node_idx_offset: int,
                edge_idx_offset: int) -> torch.Tensor:
     _need_gpu(ids, "remap_zinc")

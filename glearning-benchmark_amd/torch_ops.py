@@ -505,6 +505,42 @@ def _(ids, lens, max_num_nodes, labeled, num_node_types, edge_cap, node_cap):
     return i32(G), i32(G), i32(G), i32(G, edge_cap), i32(G, edge_cap), i32(G, edge_cap), i32(G, node_cap)
 
 
+@torch.library.custom_op("gtok::sent_decode_sizes", mutates_args=(), device_types="cuda")
+def sent_decode_sizes(ids: Tensor, lens: Tensor, max_num_nodes: int, labeled: bool, num_node_types: int,
+                      row_start: Optional[Tensor] = None, ld: int = 0) -> Tuple[Tensor, Tensor, Tensor]:
+    """gtok_sent_decode_sizes: (num_nodes, num_entries, status) int32 [rows]; ids a [rows, ld] slab (int32 / int16), or packed rows
+    (flat uint8 / int16 / int32) with row_start; ld = 0: the slab's width / every row holds its len ids."""
+    return _ops.sent_decode_sizes(ids, lens, max_num_nodes, labeled, num_node_types, row_start, ld if ld > 0 else None)
+
+
+@sent_decode_sizes.register_fake
+def _(ids, lens, max_num_nodes, labeled, num_node_types, row_start=None, ld=0):
+    i32 = lambda: ids.new_empty((lens.shape[0],), dtype=torch.int32)
+    return i32(), i32(), i32()
+
+
+@torch.library.custom_op("gtok::sent_decode_csr", mutates_args=(), device_types="cuda")
+def sent_decode_csr(ids: Tensor, lens: Tensor, max_num_nodes: int, labeled: bool, num_node_types: int, node_ptr: Tensor, edge_ptr: Tensor,
+                    total_nodes: int, total_entries: int, row_start: Optional[Tensor] = None,
+                    ld: int = 0) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """gtok_sent_decode_csr: node_ptr int32 [rows + 1] / edge_ptr int64 [rows + 1] = the prefix sums of gtok::sent_decode_sizes'
+    counts, the totals their last entries -> (rowptr int32 [N + rows], col int32 [E], eorder int32 [E], nattr uint8 [N], eattr uint8
+    [E] (both empty when unlabelled), info int32 [8] (include/gtok.h)).  Nothing is read back: the shapes are static once the
+    totals are ints."""
+    o = _ops._decode_csr_launch(ids, lens, row_start, ld if ld > 0 else None, max_num_nodes, labeled, num_node_types, node_ptr, edge_ptr,
+                                total_nodes, total_entries)
+    e = lambda t: torch.empty(0, dtype=torch.uint8, device=ids.device) if t is None else t
+    return o["rowptr"], o["col"], o["eorder"], e(o["nattr"]), e(o["eattr"]), o["info"]
+
+
+@sent_decode_csr.register_fake
+def _(ids, lens, max_num_nodes, labeled, num_node_types, node_ptr, edge_ptr, total_nodes, total_entries, row_start=None, ld=0):
+    rows = lens.shape[0]
+    e = lambda n, dt: ids.new_empty((n,), dtype=dt)
+    return (e(total_nodes + rows, torch.int32), e(total_entries, torch.int32), e(total_entries, torch.int32),
+            e(total_nodes if labeled else 0, torch.uint8), e(total_entries if labeled else 0, torch.uint8), e(8, torch.int32))
+
+
 # ---- packed (ragged) rows: include/gtok.h, "packed rows" -----------------------------------------------------------------
 @torch.library.custom_op("gtok::row_offsets", mutates_args=(), device_types="cuda")
 def row_offsets(lens: Tensor, ld: int, align: int) -> Tensor:

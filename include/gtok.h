@@ -22,6 +22,8 @@
  *   gtok_sent_packed   gtok_sent whose walk also appends every row to a packed buffer (the payload of the all-gather behind the
  *                      val / test loaders, trainer/train_agtt.py:602-607, and of the D2H copy behind :246-273) - no second pass
  *   gtok_sent_decode   the SENT spec read backwards (token rows -> graphs in visit-index space)
+ *   gtok_sent_decode_sizes / gtok_sent_decode_csr   the same, from int32 / 16-bit slabs or packed rows, a wave per row, into a
+ *                      batched CSR (gtok_csr's arrays): what a generative model's sequences are turned back into
  *   gtok_remap_zinc    trainer/train_agtt.py:171-244 on an existing token slab
  *   gtok_collate       data_loader.py:488-497 and trainer/train_agtt.py:276-302
  *                      (gather rows of a batch, pad to the batch max, bool mask)
@@ -676,6 +678,44 @@ int gtok_sent_decode(const int32_t *ids, int32_t ld, const int32_t *len, int32_t
                      int32_t *num_nodes, int32_t *num_edges, int32_t *edge_a, int32_t *edge_b,
                      int32_t *edge_type, int32_t edge_cap, int32_t *node_type, int32_t node_cap,
                      int32_t *status, void *stream);
+
+/* ---- SENT rows back to a batched CSR (gtok_csr's arrays, what GraphBatch.from_coo builds), in two passes like
+ * gtok_parse_graph_text / gtok_ids_to_text ------------------------------------------------------------------------------------
+ * Rows: row r = the first min(len[r], ld) ids at element row_start[r] of `ids` (row_start NULL: at r * ld - a [rows, ld] slab
+ * read in place), elem_bytes 1, 2 or 4 bytes each: an int32 slab, a GTOK_SENT_U16 slab, or packed rows (gtok_pack_rows_scan's
+ * row_ptr, gtok_sent_packed's row_start); a negative row_start = an empty row.  Un-remapped SENT ids only (remap_zinc folds
+ * RESET, LADJ and RADJ into one id).  4-byte ids are read as int32, as gtok_sent_decode reads them.
+ * One row becomes one graph, in visit-index space.  status[r], the node count and the edge list are those of gtok_sent_decode's
+ * state machine with unlimited capacities (status 2 cannot occur).  A status-1 row (malformed, len < 1, a negative start) is an
+ * EMPTY graph (N = 0, E = 0): rows and graphs stay index-aligned.  A status-3 row (cut before EOS) gives the part of the graph
+ * that was read; a node whose type token was cut has type 255.
+ * Entries: every decoded edge (a, b, t), in stream order, contributes the entry a -> b and then b -> a (a self loop: one entry);
+ * num_entries[r] = 2 x edges - self loops.  The CSR is what GraphBatch.from_coo builds from that list: rows ordered by source
+ * with a STABLE sort (a row lists its entries in stream order); eorder (always written) = an entry's position in its graph's
+ * interleaved list; nattr / eattr only when labelled: values 0..254 kept, everything else (a missing type included) 255.
+ * Duplicates in a stream stay duplicates: the decoder judges grammar, gtok_csr_check judges simplicity.
+ * gtok_sent_decode_sizes writes num_nodes / num_entries / status (int32 [num_rows]).  The caller prefix-sums the two counts
+ * into node_ptr int32 [num_rows + 1] / edge_ptr int64 [num_rows + 1] and allocates; gtok_sent_decode_csr READS out->node_ptr /
+ * out->edge_ptr and writes rowptr, col, eorder, nattr / eattr (labelled) and info int32 [8], which it zeroes first, laid out as
+ * gtok_csr_from_coo's where the meanings coincide:
+ *   [0] rows whose recount disagrees with their node_ptr / edge_ptr slice (or whose slice does not lie inside [0, node_ptr[rows]]
+ *       / [0, edge_ptr[rows]]): such a row is skipped, its arrays stay undefined - nothing is written outside the row's own slice
+ *       whatever the two arrays hold;
+ *   [1] max_degree, [2] max_nodes, [3] max_edges (of the rows that were built), [4] chunk_nodes, [5] chunk_edges (maxima over
+ *       aligned groups of 64 graphs of the slices' sums), [6] the number of status-1 rows, [7] 1 when some graph's interleaved list
+ *       was not already row-sorted (eorder is not the identity).
+ * One wave per row; the degree counters / row cursors of a row live in LDS, 4 bytes per node of max_num_nodes (and up to 2,048 of
+ * its entries, staged between the two halves of pass 2; a longer row is parsed once more instead).  Errors, all
+ * before anything is launched or written: GTOK_E_INVAL for null pointers, negative sizes, elem_bytes outside {1, 2, 4}, ld <= 0;
+ * GTOK_E_TOO_LARGE for max_num_nodes > GTOK_SENT_LARGE_MAX_NODES; num_rows == 0 is a no-op.  The calls only enqueue on `stream`:
+ * no allocation, no host synchronisation, no library-owned counters (they can be captured into a hipGraph).  (Added without an
+ * ABI version step, like gtok_sent_large: no struct changes - a binding learns that a library has them from the symbols.)       */
+int gtok_sent_decode_sizes(const void *ids, int32_t elem_bytes, const int64_t *row_start, int32_t ld, const int32_t *len,
+                           int32_t num_rows, int32_t max_num_nodes, int32_t labeled, int32_t num_node_types,
+                           int32_t *num_nodes, int32_t *num_entries, int32_t *status, void *stream);
+int gtok_sent_decode_csr(const void *ids, int32_t elem_bytes, const int64_t *row_start, int32_t ld, const int32_t *len,
+                         int32_t num_rows, int32_t max_num_nodes, int32_t labeled, int32_t num_node_types,
+                         const gtok_csr_built *out, void *stream);
 
 /* Which SENT kernel gtok_sent() will run for this batch ("sent_lane_kernel": lane per graph over the CSR, needs
  * GTOK_CSR_SIMPLE_SYMMETRIC, <= 64 nodes and a large batch; "sent_blane_kernel<W=..>": lane per graph over the

@@ -1,0 +1,58 @@
+// Stand-alone program over the host-side argument checks of gtok_sent_decode_sizes / gtok_sent_decode_csr
+// (csrc/gtok_sent_decode_args.hpp), to be run under the host sanitizers on a machine without a GPU:
+//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude -Iglearning-benchmark_amd/csrc \
+//       tests/host/sent_decode_args_main.cpp -o /tmp/sent_decode_args && /tmp/sent_decode_args
+// Exit status 0 and "0 failures": every check answered as include/gtok.h documents and no sanitizer spoke.
+#include <cstdio>
+#include <vector>
+
+#include "gtok_sent_decode_args.hpp"
+
+static int failures = 0;
+#define EXPECT(expr, want)                                                        \
+  do {                                                                            \
+    const int got_ = (expr);                                                      \
+    if (got_ != (want)) { std::printf("%s: %d, expected %d\n", #expr, got_, (want)); ++failures; } \
+  } while (0)
+
+int main() {
+  std::vector<int32_t> ids(64, 5), len(4, 16);
+  const void *p = ids.data();
+  const int32_t *l = len.data();
+  using gtok::sent_decode_check_rows;
+  EXPECT(sent_decode_check_rows(p, 4, 16, l, 4, 37, 9), GTOK_OK);
+  EXPECT(sent_decode_check_rows(p, 2, 16, l, 4, 37, 9), GTOK_OK);
+  EXPECT(sent_decode_check_rows(p, 1, 16, l, 4, GTOK_SENT_LARGE_MAX_NODES, 0), GTOK_OK);
+  for (int eb : {-1, 0, 3, 5, 8}) EXPECT(sent_decode_check_rows(p, eb, 16, l, 4, 37, 9), GTOK_E_INVAL);
+  EXPECT(sent_decode_check_rows(p, 4, 0, l, 4, 37, 9), GTOK_E_INVAL);
+  EXPECT(sent_decode_check_rows(p, 4, -7, l, 4, 37, 9), GTOK_E_INVAL);
+  EXPECT(sent_decode_check_rows(p, 4, 16, l, -1, 37, 9), GTOK_E_INVAL);
+  EXPECT(sent_decode_check_rows(p, 4, 16, l, 4, -1, 9), GTOK_E_INVAL);
+  EXPECT(sent_decode_check_rows(p, 4, 16, l, 4, 37, -1), GTOK_E_INVAL);
+  EXPECT(sent_decode_check_rows(p, 4, 16, l, 4, GTOK_SENT_LARGE_MAX_NODES + 1, 9), GTOK_E_TOO_LARGE);
+  EXPECT(sent_decode_check_rows(p, 4, 16, l, 4, 0x7FFFFFFF, 9), GTOK_E_TOO_LARGE);
+  EXPECT(sent_decode_check_rows(nullptr, 4, 16, l, 4, 37, 9), GTOK_E_INVAL);
+  EXPECT(sent_decode_check_rows(p, 4, 16, nullptr, 4, 37, 9), GTOK_E_INVAL);
+  EXPECT(sent_decode_check_rows(nullptr, 4, 16, nullptr, 0, 37, 9), 1);      // no rows: nothing to do, whatever the pointers
+  EXPECT(sent_decode_check_rows(nullptr, 3, 16, nullptr, 0, 37, 9), GTOK_E_INVAL);
+
+  std::vector<int32_t> a(8);
+  std::vector<int64_t> e(8);
+  std::vector<uint8_t> b(8);
+  gtok_csr_built out = {a.data(), e.data(), a.data(), a.data(), a.data(), b.data(), b.data(), a.data()};
+  using gtok::sent_decode_check_out;
+  EXPECT(sent_decode_check_out(&out, 1), GTOK_OK);
+  EXPECT(sent_decode_check_out(nullptr, 0), GTOK_E_INVAL);
+  gtok_csr_built o2 = out;
+  o2.nattr = nullptr; o2.eattr = nullptr;
+  EXPECT(sent_decode_check_out(&o2, 0), GTOK_OK);
+  EXPECT(sent_decode_check_out(&o2, 1), GTOK_E_INVAL);
+  int32_t *gtok_csr_built::*const need32[] = {&gtok_csr_built::node_ptr, &gtok_csr_built::rowptr, &gtok_csr_built::col, &gtok_csr_built::eorder,
+                                              &gtok_csr_built::info};
+  for (auto m : need32) { gtok_csr_built o3 = out; o3.*m = nullptr; EXPECT(sent_decode_check_out(&o3, 0), GTOK_E_INVAL); }
+  gtok_csr_built o4 = out;
+  o4.edge_ptr = nullptr;
+  EXPECT(sent_decode_check_out(&o4, 0), GTOK_E_INVAL);
+  std::printf("%d failures\n", failures);
+  return failures ? 1 : 0;
+}
