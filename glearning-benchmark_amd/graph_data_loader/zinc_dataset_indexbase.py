@@ -41,6 +41,7 @@ class ZINCTokenizationDataset(Dataset):
         self.zinc_dataset = zinc_dataset
         self._batch: Optional[GraphBatch] = None
         self._texts = self._labels = None
+        self._vocab: Optional[Dict[str, int]] = None
         self._bulk = True                 # render the split at once on the first fetch when a GPU is there
         print(f"Loaded ZINC {split} split: {len(self.zinc_dataset)} molecules")
 
@@ -152,7 +153,20 @@ class ZINCTokenizationDataset(Dataset):
             device = torch.device("cuda", torch.cuda.current_device())
         batch = self.graph_batch(device)
         lut = _ops.zinc_lut(vocab, max(batch.max_nodes, 1))
+        self._vocab = vocab                                        # decode_batch reads rows with the vocab that wrote them
         return _ops.ibtt_zinc(batch, lut, max_len, vocab["<pad>"], ld=ld)
+
+    def decode_batch(self, ids: torch.Tensor, ln: torch.Tensor, vocab: Optional[Dict[str, int]] = None,
+                     row_start: Optional[torch.Tensor] = None, check_symmetric: bool = False) -> Tuple[GraphBatch, torch.Tensor]:
+        """Rows of this grammar (tokenize()'s, or a model's) back to molecules on the rows' device: (GraphBatch, status int32
+        [rows]) - ops.ibtt_decode_csr with the vocab of the last tokenize() call (or `vocab`) and node indices up to the split's
+        largest molecule.  status: 0 complete, 1 malformed (an empty graph), 3 a well-formed prefix."""
+        vocab = self._vocab if vocab is None else vocab
+        if vocab is None:
+            raise RuntimeError("decode_batch: no vocab - call tokenize(vocab) first or pass vocab=")
+        num_ids = max(self.graph_batch(ids.device if ids.device.type == "cuda" else None).max_nodes, 1)
+        inv = _ops.ibtt_inverse_lut(_ops.zinc_lut(vocab, num_ids), max(vocab.values()) + 1, vocab["<pad>"])
+        return _ops.ibtt_decode_csr(ids, ln, "zinc", inv, num_ids, row_start=row_start, check_symmetric=check_symmetric)
 
 
 def collate_zinc_batch(batch, pad_id):

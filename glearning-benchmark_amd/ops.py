@@ -877,6 +877,131 @@ def sent_decode_csr(ids: torch.Tensor, ln: torch.Tensor, max_num_nodes: int, lab
     return b, status
 
 
+# ------------------------------------------------------------------------------------------------
+# IBTT rows -> CSR (include/gtok.h: gtok_ibtt_decode_sizes / gtok_ibtt_decode_csr)
+# ------------------------------------------------------------------------------------------------
+IBTT_GRAMMARS = {"zinc": _lib.IBTT_GRAMMAR_ZINC, "synth": _lib.IBTT_GRAMMAR_SYNTH}
+
+
+def _ibtt_grammar(grammar) -> int:
+    g = IBTT_GRAMMARS.get(grammar, grammar)
+    if g not in (_lib.IBTT_GRAMMAR_ZINC, _lib.IBTT_GRAMMAR_SYNTH):
+        raise ValueError("grammar is 'zinc' / 'synth' (or GTOK_IBTT_GRAMMAR_ZINC / _SYNTH)")
+    return int(g)
+
+
+def ibtt_inverse_lut(lut, vocab_size: int, pad_id: Optional[int] = None) -> torch.Tensor:
+    """The vocab of the IBTT decoder, built on the host from the LUT the rows were tokenized with (zinc_lut / synth_lut):
+    int32 [vocab_size], inv[id] = the LUT slot that holds id, -1 for an id no slot holds AND for an id that two slots share
+    (vocab['<pad>'] when tokens are absent from the vocab: such an id names no token).  pad_id: that id, -1 whatever holds it (one
+    absent token alone would otherwise own it).  LUT ids outside [0, vocab_size) have no entry.  A host tensor; ibtt_decode_*
+    move it to the rows' device."""
+    lut = np.asarray(lut.cpu() if isinstance(lut, torch.Tensor) else lut, dtype=np.int64).reshape(-1)
+    vocab_size = int(vocab_size)
+    if vocab_size < 1:
+        raise ValueError("vocab_size must be positive")
+    inv = np.full(vocab_size, -1, np.int32)
+    ok = (lut >= 0) & (lut < vocab_size)
+    owners = np.bincount(lut[ok], minlength=vocab_size)
+    slots = np.nonzero(ok)[0]
+    inv[lut[slots]] = slots
+    inv[owners != 1] = -1
+    if pad_id is not None and 0 <= int(pad_id) < vocab_size:
+        inv[int(pad_id)] = -1
+    return torch.from_numpy(inv)
+
+
+def _need_ibtt_decode() -> None:
+    if not all(hasattr(lib(), n) for n in _lib.IBTT_DECODE_SYMBOLS):
+        raise _lib.GtokError(f"{_lib.LIB_PATH} has no gtok_ibtt_decode_sizes / gtok_ibtt_decode_csr: it was built before they were added")
+
+
+def _ibtt_inv(inv: torch.Tensor, dev) -> torch.Tensor:
+    if inv.dim() != 1 or inv.numel() < 1:
+        raise ValueError("inv is a non-empty int32 vector (ibtt_inverse_lut)")
+    return inv.to(dev, dtype=torch.int32).contiguous()
+
+
+def ibtt_decode_sizes(ids: torch.Tensor, ln: torch.Tensor, grammar, inv: torch.Tensor, max_num_nodes: int,
+                      row_start: Optional[torch.Tensor] = None, ld: Optional[int] = None, with_query: bool = False):
+    """gtok_ibtt_decode_sizes: (num_nodes, num_entries, status) int32 [rows] of IBTT rows - the sizes of the graphs
+    ibtt_decode_csr builds (a status-1 row: 0, 0) - and, with_query (graph-token rows), query int32 [rows, 4].  ids / row_start /
+    ld as sent_decode_csr.  Nothing is read back."""
+    eb, ld, rows = _decode_rows(ids, ln, row_start, ld, "ibtt_decode_sizes")
+    _need_ibtt_decode()
+    g = _ibtt_grammar(grammar)
+    dev = ids.device
+    inv = _ibtt_inv(inv, dev)
+    nn, ne, st = (torch.empty(rows, dtype=torch.int32, device=dev) for _ in range(3))
+    query = torch.zeros((rows, 4), dtype=torch.int32, device=dev) if with_query else None
+    if rows:
+        check(lib().gtok_ibtt_decode_sizes(ids.data_ptr(), eb, None if row_start is None else row_start.data_ptr(), ld, ln.data_ptr(), rows,
+                                           g, inv.data_ptr(), inv.numel(), int(max_num_nodes), nn.data_ptr(), ne.data_ptr(), st.data_ptr(),
+                                           query.data_ptr() if with_query and g == _lib.IBTT_GRAMMAR_SYNTH else None, _stream(dev)),
+              "gtok_ibtt_decode_sizes")
+    return (nn, ne, st, query) if with_query else (nn, ne, st)
+
+
+def _ibtt_decode_csr_launch(ids, ln, row_start, ld, grammar, inv, max_num_nodes, node_ptr, edge_ptr, N: int, E: int) -> dict:
+    """gtok_ibtt_decode_csr on the current stream into fresh arrays of the given totals: -> dict of gtok_csr_built's arrays
+    (nattr / eattr None for graph-token rows); no host read."""
+    eb, ld, rows = _decode_rows(ids, ln, row_start, ld, "ibtt_decode_csr")
+    _need_ibtt_decode()
+    g = _ibtt_grammar(grammar)
+    dev = ids.device
+    inv = _ibtt_inv(inv, dev)
+    if node_ptr.dtype != torch.int32 or edge_ptr.dtype != torch.int64 or node_ptr.numel() != rows + 1 or edge_ptr.numel() != rows + 1 \
+            or not node_ptr.is_contiguous() or not edge_ptr.is_contiguous() or node_ptr.device != dev or edge_ptr.device != dev:
+        raise ValueError("ibtt_decode_csr: node_ptr int32 [rows + 1] and edge_ptr int64 [rows + 1] on the rows' device")
+    N, E = int(N), int(E)
+    if N < 0 or E < 0 or N + rows >= 2 ** 31:
+        raise ValueError("ibtt_decode_csr: totals out of range (a batch holds fewer than 2^31 nodes + graphs; shard it)")
+    typed = g == _lib.IBTT_GRAMMAR_ZINC
+    new = lambda n, dt: torch.empty(n + 1, dtype=dt, device=dev)      # (one spare element: an empty tensor has no address)
+    full = dict(node_ptr=node_ptr, edge_ptr=edge_ptr, rowptr=new(N + rows, torch.int32), col=new(E, torch.int32), eorder=new(E, torch.int32),
+                nattr=new(N, torch.uint8) if typed else None, eattr=new(E, torch.uint8) if typed else None, info=new(8, torch.int32))
+    o = {k: t if t is None or k in ("node_ptr", "edge_ptr") else t[:-1] for k, t in full.items()}
+    if rows == 0:
+        o["info"].zero_()
+        return o
+    ptr = lambda t: None if t is None else t.data_ptr()
+    cout = _lib.GtokCsrBuilt(*[ptr(full[n]) for n, _ in _lib.GtokCsrBuilt._fields_])
+    check(lib().gtok_ibtt_decode_csr(ids.data_ptr(), eb, ptr(row_start), ld, ln.data_ptr(), rows, g, inv.data_ptr(), inv.numel(),
+                                     int(max_num_nodes), ctypes.byref(cout), _stream(dev)), "gtok_ibtt_decode_csr")
+    return o
+
+
+def ibtt_decode_csr(ids: torch.Tensor, ln: torch.Tensor, grammar, inv: torch.Tensor, max_num_nodes: int,
+                    row_start: Optional[torch.Tensor] = None, ld: Optional[int] = None, check_symmetric: bool = False):
+    """IBTT rows -> (GraphBatch on the rows' device, status int32 [rows]) for grammar 'zinc', plus query int32 [rows, 4] for
+    grammar 'synth': row r becomes graph r in the input's own node numbering and edge order (include/gtok.h:
+    gtok_ibtt_decode_sizes / gtok_ibtt_decode_csr).  status: 0 complete, 1 malformed (an empty graph), 3 a well-formed prefix
+    (the part that was read).  inv: ibtt_inverse_lut of the LUT the rows were tokenized with.  ids / row_start / ld as
+    sent_decode_csr; every row must lie inside `ids`: that is not checked.  Two read-backs: the two totals after the sizing
+    pass, `info` after the build; check_symmetric as sent_decode_csr (a third)."""
+    g = _ibtt_grammar(grammar)
+    synth = g == _lib.IBTT_GRAMMAR_SYNTH
+    sizes = ibtt_decode_sizes(ids, ln, g, inv, max_num_nodes, row_start, ld, with_query=synth)
+    nn, ne, status = sizes[:3]
+    dev, rows = ids.device, int(ln.numel())
+    node_ptr64 = torch.zeros(rows + 1, dtype=torch.int64, device=dev); torch.cumsum(nn, 0, dtype=torch.int64, out=node_ptr64[1:])
+    edge_ptr = torch.zeros(rows + 1, dtype=torch.int64, device=dev); torch.cumsum(ne, 0, dtype=torch.int64, out=edge_ptr[1:])
+    N, E = torch.stack([node_ptr64[-1], edge_ptr[-1]]).tolist()            # the read-back of the two totals
+    if N + rows >= 2 ** 31:
+        raise ValueError("batch too large for int32 node offsets; shard it")
+    o = _ibtt_decode_csr_launch(ids, ln, row_start, ld, g, inv, max_num_nodes, node_ptr64.to(torch.int32), edge_ptr, N, E)
+    v = o["info"].tolist()                                                  # ... and of info
+    if v[0]:
+        raise _lib.GtokError(f"ibtt_decode_csr: {v[0]} rows changed between the two passes")
+    b = GraphBatch(rows, v[2], v[3], o["node_ptr"], o["edge_ptr"], o["rowptr"], o["col"], o["eorder"] if v[7] else None, o["nattr"], o["eattr"],
+                   0, v[4], v[5], v[1] if N else 0)
+    if check_symmetric and E:
+        if csr_check(b)["violations"] == 0:
+            b.flags |= _lib.CSR_SIMPLE_SYMMETRIC
+        b.checked = True
+    return (b, status, sizes[3]) if synth else (b, status)
+
+
 def remap_zinc(ids: torch.Tensor, ln: torch.Tensor, idx_offset: int, node_idx_offset: int,
                edge_idx_offset: int) -> torch.Tensor:
     _need_gpu(ids, "remap_zinc")

@@ -541,6 +541,42 @@ def _(ids, lens, max_num_nodes, labeled, num_node_types, node_ptr, edge_ptr, tot
             e(total_nodes if labeled else 0, torch.uint8), e(total_entries if labeled else 0, torch.uint8), e(8, torch.int32))
 
 
+@torch.library.custom_op("gtok::ibtt_decode_sizes", mutates_args=(), device_types="cuda")
+def ibtt_decode_sizes(ids: Tensor, lens: Tensor, grammar: int, inv: Tensor, max_num_nodes: int,
+                      row_start: Optional[Tensor] = None, ld: int = 0) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """gtok_ibtt_decode_sizes: (num_nodes, num_entries, status int32 [rows], query int32 [rows, 4] - zeros for grammar 0, the
+    molecules); grammar = GTOK_IBTT_GRAMMAR_*; inv = ops.ibtt_inverse_lut; ids / row_start / ld as gtok::sent_decode_sizes."""
+    return _ops.ibtt_decode_sizes(ids, lens, grammar, inv, max_num_nodes, row_start, ld if ld > 0 else None, with_query=True)
+
+
+@ibtt_decode_sizes.register_fake
+def _(ids, lens, grammar, inv, max_num_nodes, row_start=None, ld=0):
+    i32 = lambda *s: ids.new_empty(s, dtype=torch.int32)
+    rows = lens.shape[0]
+    return i32(rows), i32(rows), i32(rows), i32(rows, 4)
+
+
+@torch.library.custom_op("gtok::ibtt_decode_csr", mutates_args=(), device_types="cuda")
+def ibtt_decode_csr(ids: Tensor, lens: Tensor, grammar: int, inv: Tensor, max_num_nodes: int, node_ptr: Tensor, edge_ptr: Tensor,
+                    total_nodes: int, total_entries: int, row_start: Optional[Tensor] = None,
+                    ld: int = 0) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """gtok_ibtt_decode_csr: as gtok::sent_decode_csr -> (rowptr, col, eorder, nattr, eattr (both empty for grammar 1, the
+    graph-token rows), info int32 [8]).  Nothing is read back."""
+    o = _ops._ibtt_decode_csr_launch(ids, lens, row_start, ld if ld > 0 else None, grammar, inv, max_num_nodes, node_ptr, edge_ptr,
+                                     total_nodes, total_entries)
+    e = lambda t: torch.empty(0, dtype=torch.uint8, device=ids.device) if t is None else t
+    return o["rowptr"], o["col"], o["eorder"], e(o["nattr"]), e(o["eattr"]), o["info"]
+
+
+@ibtt_decode_csr.register_fake
+def _(ids, lens, grammar, inv, max_num_nodes, node_ptr, edge_ptr, total_nodes, total_entries, row_start=None, ld=0):
+    rows = lens.shape[0]
+    typed = grammar == 0
+    e = lambda n, dt: ids.new_empty((n,), dtype=dt)
+    return (e(total_nodes + rows, torch.int32), e(total_entries, torch.int32), e(total_entries, torch.int32),
+            e(total_nodes if typed else 0, torch.uint8), e(total_entries if typed else 0, torch.uint8), e(8, torch.int32))
+
+
 # ---- packed (ragged) rows: include/gtok.h, "packed rows" -----------------------------------------------------------------
 @torch.library.custom_op("gtok::row_offsets", mutates_args=(), device_types="cuda")
 def row_offsets(lens: Tensor, ld: int, align: int) -> Tensor:

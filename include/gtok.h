@@ -717,6 +717,47 @@ int gtok_sent_decode_csr(const void *ids, int32_t elem_bytes, const int64_t *row
                          int32_t num_rows, int32_t max_num_nodes, int32_t labeled, int32_t num_node_types,
                          const gtok_csr_built *out, void *stream);
 
+/* ---- IBTT rows back to a batched CSR: the same two passes, outputs and row formats as the SENT pair above ---------------------
+ * Rows: exactly as gtok_sent_decode_csr reads them (row_start / ld / len / elem_bytes; a negative start or fewer than one id:
+ * status 1).  `grammar` says which serialiser wrote them.  The vocab is an input: inv[id], 0 <= id < inv_len, is the LUT slot of
+ * that id (GTOK_ZLUT_* / GTOK_SLUT_*; a slot >= *_NODE0 is node index slot - NODE0) or -1; the caller builds it on the host from
+ * the LUT it tokenized with, an id that two slots share (pad_id, when a token is absent from the vocab) gets -1.  An id outside
+ * [0, inv_len) or with inv[id] < 0 has class -1 and matches nothing.  c[i] below = the class of token i, L = the row's ids.
+ * IBTT lists node indices in the input's own numbering and edges in the input's own order: a decoded row is the input graph.
+ * status[r]: 0 complete, 1 malformed (an EMPTY graph, N = 0, E = 0: rows and graphs stay index-aligned), 3 a well-formed prefix
+ * (the part that was read is built); 2 does not occur.
+ * GTOK_IBTT_GRAMMAR_ZINC  "<bos> (<atom> sym)* (<bond> type u v)* <q> regression <p>":
+ *   a last token of class EOS is dropped and remembered (L' = L - 1: the max_len cut writes <eos> over the last kept token); L' == 0
+ *   then: status 3, empty.  c[0] must be BOS.  A = the longest run of atom records (c[1+2k] == ATOM, c[2+2k] in [ATOM0, ATOM0+9],
+ *   both inside L'); N = A, node type slot - ATOM0, 255 for 'X'.  B = the longest run of bond records from p = 1 + 2A (c[p+4k] ==
+ *   BOND, c[p+4k+1] in [BOND0, BOND0+4], the next two node slots of index < N, all four inside L'); type slot - BOND0.  The rest
+ *   c[p+4B .. L'): [Q, REGRESSION, P] is status 0 (status 1 when an EOS was dropped); a proper prefix of that, a proper prefix of a
+ *   bond record valid so far, or - when B == 0 - a lone ATOM is status 3; anything else status 1.  N > max_num_nodes: status 1.
+ *   Entries: bond k = (u, v, t) contributes u -> v and then v -> u (a self loop: one entry): num_entries = 2B - self loops.
+ * GTOK_IBTT_GRAMMAR_SYNTH "<bos> (u v <e>)* <n> 0 1 .. N-1 <q> [q0 [q1 [q2]]] <p>":
+ *   c[0] must be BOS.  M = the longest run of edge records (c[1+3k], c[2+3k] node slots, c[3+3k] == E, inside L); p = 1 + 3M.
+ *   p == L: status 3.  c[p] != N: status 3 when c[p..L) is one or two node slots, else 1.  Otherwise S = the longest run with
+ *   c[p+1+k] == NODE0 + k, q = p + 1 + S; q == L: status 3; c[q] != Q: status 1; c[L-1] == P with nq = L - q - 2 in 0..3: status
+ *   0; else L - q - 1 <= 3: status 3 (cut inside the query); else status 1.  Once Q was seen N = S and an endpoint >= S is
+ *   status 1; before it N = max(S, 1 + the largest endpoint of the M records).  N > max_num_nodes: status 1.
+ *   Entries: one entry u -> v per edge record, in list order (what gtok_csr keeps of a graph-token edge list).
+ *   query (int32 [num_rows, 4], NULL = skip; sizes pass): gtok_ibtt_synth's input read back from a status-0 row - query[4r] = nq,
+ *   query[4r+1 ..] = the raw ids after <q>, unused slots 0; all 0 for any other row.
+ * The CSR, info[8], the skipping of a row whose recount disagrees with its slice and the errors are gtok_sent_decode_csr's; ZINC
+ * writes (and needs) nattr / eattr, SYNTH neither.  Also GTOK_E_INVAL: a grammar outside {0, 1}, inv NULL, inv_len <= 0.  One wave
+ * per row, a lane per record; the degree counters / row cursors live in LDS, 4 bytes per node of max_num_nodes (hence
+ * max_num_nodes <= GTOK_SENT_LARGE_MAX_NODES); nothing is staged, pass 2 reads a row's tokens three times.  Nothing is read through
+ * an index that has not been range-checked; row_start and len are trusted, as by every packed-row reader.  The calls only enqueue
+ * on `stream`: no allocation, no host synchronisation, no library-owned counters.  (Added without an ABI version step.)            */
+#define GTOK_IBTT_GRAMMAR_ZINC  0   /* gtok_ibtt_zinc's rows  */
+#define GTOK_IBTT_GRAMMAR_SYNTH 1   /* gtok_ibtt_synth's rows */
+int gtok_ibtt_decode_sizes(const void *ids, int32_t elem_bytes, const int64_t *row_start, int32_t ld, const int32_t *len,
+                           int32_t num_rows, int32_t grammar, const int32_t *inv, int32_t inv_len, int32_t max_num_nodes,
+                           int32_t *num_nodes, int32_t *num_entries, int32_t *status, int32_t *query, void *stream);
+int gtok_ibtt_decode_csr(const void *ids, int32_t elem_bytes, const int64_t *row_start, int32_t ld, const int32_t *len,
+                         int32_t num_rows, int32_t grammar, const int32_t *inv, int32_t inv_len, int32_t max_num_nodes,
+                         const gtok_csr_built *out, void *stream);
+
 /* Which SENT kernel gtok_sent() will run for this batch ("sent_lane_kernel": lane per graph over the CSR, needs
  * GTOK_CSR_SIMPLE_SYMMETRIC, <= 64 nodes and a large batch; "sent_blane_kernel<W=..>": lane per graph over the
  * adjacency bit-matrix mirror, unlabelled, <= 256 nodes; "sent_reg_kernel": wave per graph, <= 64 nodes;

@@ -1,0 +1,68 @@
+// Stand-alone program over the host-side argument checks of gtok_ibtt_decode_sizes / gtok_ibtt_decode_csr
+// (csrc/gtok_ibtt_decode_args.hpp), to be run under the host sanitizers on a machine without a GPU:
+//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude -Iglearning-benchmark_amd/csrc \
+//       tests/host/ibtt_decode_args_main.cpp -o /tmp/ibtt_decode_args && /tmp/ibtt_decode_args
+// Exit status 0 and "0 failures": every check answered as include/gtok.h documents and no sanitizer spoke.
+#include <cstdio>
+#include <vector>
+
+#include "gtok_ibtt_decode_args.hpp"
+
+static int failures = 0;
+#define EXPECT(expr, want)                                                        \
+  do {                                                                            \
+    const int got_ = (expr);                                                      \
+    if (got_ != (want)) { std::printf("%s: %d, expected %d\n", #expr, got_, (want)); ++failures; } \
+  } while (0)
+
+int main() {
+  std::vector<int32_t> ids(64, 5), len(4, 16), inv(32, -1);
+  const void *p = ids.data();
+  const int32_t *l = len.data(), *v = inv.data();
+  const int Z = GTOK_IBTT_GRAMMAR_ZINC, S = GTOK_IBTT_GRAMMAR_SYNTH;
+  using gtok::ibtt_decode_check_rows;
+  EXPECT(ibtt_decode_check_rows(p, 4, 16, l, 4, Z, v, 32, 37), GTOK_OK);
+  EXPECT(ibtt_decode_check_rows(p, 2, 16, l, 4, S, v, 32, 37), GTOK_OK);
+  EXPECT(ibtt_decode_check_rows(p, 1, 16, l, 4, S, v, 1, GTOK_SENT_LARGE_MAX_NODES), GTOK_OK);
+  EXPECT(ibtt_decode_check_rows(p, 4, 16, l, 4, Z, v, 32, 0), GTOK_OK);
+  for (int eb : {-1, 0, 3, 5, 8}) EXPECT(ibtt_decode_check_rows(p, eb, 16, l, 4, Z, v, 32, 37), GTOK_E_INVAL);
+  for (int g : {-1, 2, 7}) EXPECT(ibtt_decode_check_rows(p, 4, 16, l, 4, g, v, 32, 37), GTOK_E_INVAL);
+  EXPECT(ibtt_decode_check_rows(p, 4, 0, l, 4, Z, v, 32, 37), GTOK_E_INVAL);
+  EXPECT(ibtt_decode_check_rows(p, 4, -7, l, 4, Z, v, 32, 37), GTOK_E_INVAL);
+  EXPECT(ibtt_decode_check_rows(p, 4, 16, l, -1, Z, v, 32, 37), GTOK_E_INVAL);
+  EXPECT(ibtt_decode_check_rows(p, 4, 16, l, 4, Z, v, 32, -1), GTOK_E_INVAL);
+  EXPECT(ibtt_decode_check_rows(p, 4, 16, l, 4, Z, v, 0, 37), GTOK_E_INVAL);
+  EXPECT(ibtt_decode_check_rows(p, 4, 16, l, 4, S, v, -3, 37), GTOK_E_INVAL);
+  EXPECT(ibtt_decode_check_rows(p, 4, 16, l, 4, Z, v, 32, GTOK_SENT_LARGE_MAX_NODES + 1), GTOK_E_TOO_LARGE);
+  EXPECT(ibtt_decode_check_rows(p, 4, 16, l, 4, S, v, 32, 0x7FFFFFFF), GTOK_E_TOO_LARGE);
+  EXPECT(ibtt_decode_check_rows(nullptr, 4, 16, l, 4, Z, v, 32, 37), GTOK_E_INVAL);
+  EXPECT(ibtt_decode_check_rows(p, 4, 16, nullptr, 4, Z, v, 32, 37), GTOK_E_INVAL);
+  EXPECT(ibtt_decode_check_rows(p, 4, 16, l, 4, Z, nullptr, 32, 37), GTOK_E_INVAL);
+  EXPECT(ibtt_decode_check_rows(nullptr, 4, 16, nullptr, 0, S, nullptr, 32, 37), 1);      // no rows: nothing to do, whatever the pointers
+  EXPECT(ibtt_decode_check_rows(nullptr, 3, 16, nullptr, 0, Z, nullptr, 32, 37), GTOK_E_INVAL);
+  EXPECT(ibtt_decode_check_rows(nullptr, 4, 16, nullptr, 0, 2, nullptr, 32, 37), GTOK_E_INVAL);
+
+  std::vector<int32_t> a(8);
+  std::vector<int64_t> e(8);
+  std::vector<uint8_t> b(8);
+  gtok_csr_built out = {a.data(), e.data(), a.data(), a.data(), a.data(), b.data(), b.data(), a.data()};
+  using gtok::ibtt_decode_check_out;
+  EXPECT(ibtt_decode_check_out(&out, Z), GTOK_OK);
+  EXPECT(ibtt_decode_check_out(&out, S), GTOK_OK);
+  EXPECT(ibtt_decode_check_out(nullptr, S), GTOK_E_INVAL);
+  gtok_csr_built o2 = out;
+  o2.nattr = nullptr; o2.eattr = nullptr;
+  EXPECT(ibtt_decode_check_out(&o2, S), GTOK_OK);            // graph-token rows carry no types
+  EXPECT(ibtt_decode_check_out(&o2, Z), GTOK_E_INVAL);
+  gtok_csr_built o5 = out;
+  o5.eattr = nullptr;
+  EXPECT(ibtt_decode_check_out(&o5, Z), GTOK_E_INVAL);
+  int32_t *gtok_csr_built::*const need32[] = {&gtok_csr_built::node_ptr, &gtok_csr_built::rowptr, &gtok_csr_built::col, &gtok_csr_built::eorder,
+                                              &gtok_csr_built::info};
+  for (auto m : need32) { gtok_csr_built o3 = out; o3.*m = nullptr; EXPECT(ibtt_decode_check_out(&o3, S), GTOK_E_INVAL); }
+  gtok_csr_built o4 = out;
+  o4.edge_ptr = nullptr;
+  EXPECT(ibtt_decode_check_out(&o4, S), GTOK_E_INVAL);
+  std::printf("%d failures\n", failures);
+  return failures ? 1 : 0;
+}
