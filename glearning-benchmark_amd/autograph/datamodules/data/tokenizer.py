@@ -102,14 +102,53 @@ class Graph2TrailTokenizer:
                          epochs=epochs, u16=u16)
 
     # ---- the way back: sequences -> graphs
+    def visit_order(self, batch: "GraphBatch", epoch: int = 0, epochs: int = 1, graph_base: int = 0) -> torch.Tensor:
+        """visit_index int32 [K, N_total] of the trails tokenize_batch writes for the same (epoch, graph_base): node u of graph g was
+        the visit_index[e, node_ptr[g] + u]-th node its trail of epoch + e visited (position id 6 + that), -1 where a trail cut at the
+        truncation length never got.  ops.sent_order with this tokenizer's seed, lengths and labeled_graph; what decode_batch_like
+        needs to hand graphs back in the input's numbering."""
+        if self.max_num_nodes is None:
+            raise RuntimeError("call set_num_nodes() first")
+        return _ops.sent_order(batch, self._max_len(), self.seed, epoch, epochs=epochs, graph_base=graph_base, max_num_nodes=self.max_num_nodes,
+                               labeled=self.labeled_graph, num_node_types=self.num_node_types, num_edge_types=self.num_edge_types)
+
     def decode_batch(self, ids: torch.Tensor, ln: torch.Tensor, row_start: Optional[torch.Tensor] = None, check_symmetric: bool = False):
         """Un-remapped rows (tokenize_batch's slabs, int32 or 16-bit, or packed rows with row_start) -> (GraphBatch, status int32
         [rows]) on the device: ops.sent_decode_csr with this tokenizer's max_num_nodes, labeled_graph and num_node_types.  Graph r is
-        row r in visit-index space; status 0 complete, 1 malformed (an empty graph), 3 cut before EOS."""
+        row r in visit-index space; status 0 complete, 1 malformed (an empty graph), 3 cut before EOS.  decode_batch_like hands the
+        graphs back in the input's own node numbering."""
         if self.max_num_nodes is None:
             raise RuntimeError("call set_num_nodes() first")
         return _ops.sent_decode_csr(ids, ln, self.max_num_nodes, labeled=self.labeled_graph, num_node_types=self.num_node_types,
                                     row_start=row_start, check_symmetric=check_symmetric)
+
+    def decode_batch_like(self, ids: torch.Tensor, ln: torch.Tensor, like: "GraphBatch", order: torch.Tensor,
+                          row_start: Optional[torch.Tensor] = None, check_symmetric: bool = False):
+        """decode_batch whose graphs come back in the numbering of `like`, the GraphBatch that was tokenized: order = visit_order's
+        result for these rows ([K, N_total], epoch slice e for rows e * G .. e * G + G - 1).  -> (GraphBatch, status): `like`'s node
+        counts (K times over), rows in ascending column (ops.csr_relabel); a node a cut row never reached is isolated, type 255.
+        ops.graphs_equal then compares the result with the input - with its symmetric closure, where the input lists every edge
+        once.  status is the decoder's; rows and an order of different walks (another seed, epoch, graph_base, max length) raise."""
+        b, status = self.decode_batch(ids, ln, row_start=row_start)
+        G, N = like.num_graphs, like.num_nodes_total
+        K = b.num_graphs // G if G else 1
+        if b.num_graphs != K * G or int(order.numel()) != K * N:
+            raise ValueError(f"decode_batch_like: {b.num_graphs} rows and {int(order.numel())} order entries for a batch of {G} graphs, {N} nodes")
+        dev = b.device
+        node_ptr = like.node_ptr.to(dev)
+        counts = (node_ptr[1:] - node_ptr[:-1]).repeat(K)
+        target_ptr = torch.zeros(K * G + 1, dtype=torch.int32, device=dev)
+        torch.cumsum(counts, 0, dtype=torch.int32, out=target_ptr[1:])
+        # (an index at or beyond a cut row's decoded node count names a visit whose position token the cut removed: it lies outside
+        # [0, N_old) and gtok_csr_relabel reads it as absent)
+        out, st = _ops.csr_relabel(b, order.to(dev, dtype=torch.int32).reshape(-1), target_ptr, like.max_nodes)
+        if int((st == 1).sum()):
+            raise GtokError("decode_batch_like: the visit order does not fit the rows (other seed, epoch, graph_base or max length?)")
+        if check_symmetric and out.num_edges_total:
+            if _ops.csr_check(out)["violations"] == 0:
+                out.flags |= _ops._lib.CSR_SIMPLE_SYMMETRIC
+            out.checked = True
+        return out, status
 
     def decode(self, tokens) -> dict:
         """One sequence (a 1-D tensor of un-remapped ids, as tokenizer(data) returns them) -> dict(num_nodes, edge_index int64 [2, E]

@@ -16,6 +16,9 @@
 // Nothing of the slice is read through a const __restrict__ pointer (the scalar cache would return stale bytes): only the
 // caller's immutable CSR arrays go that way.
 // Separate translation unit: the register allocation of gtok_sent.hip's kernels is untouched by it.
+// gtok_sent_large_order runs the same walk through instantiations of their own (ORD = 1: rows and the visit order, ORD = 2: the
+// order alone, no token leaves the wave): when a walk ends the wave copies its node -> visit index table from LDS to the caller's
+// array.  The ORD = 0 instantiations are gtok_sent_large's, compiled as before (profiles/sent_order/kernel_resources.md).
 #include "gtok_common.hpp"
 #include "gtok.h"
 #include "gtok_sent_reg.hpp"
@@ -37,6 +40,8 @@ struct LargeArgs {
   int maxn, maxe;         // the batch's claims: a graph beyond them is clamped to them (the slice and the LDS tables are sized by them)
   int nw;                 // 32-bit words of a set in LDS
   int pairs;              // (graph, epoch) pairs, epoch-major
+  int32_t *visit_index;   // gtok_sent_large_order only: [K, order_stride], epoch-major
+  int64_t order_stride;   // elements
 };
 
 __device__ __forceinline__ void slice_sync() {   // stores to the slice drained before another lane loads them
@@ -103,8 +108,12 @@ __device__ __forceinline__ int select_kth(F word_at, int wlo, int whi, int k) {
   return -1;
 }
 
-template <bool LAB>
+// ORD: 0 = the rows (gtok_sent_large), 1 = the rows and the visit order, 2 = the visit order alone (tokens are counted, not stored,
+// and no type is looked up)
+template <bool LAB, int ORD = 0>
 __global__ void __launch_bounds__(64) sent_large_kernel(const LargeArgs a) {
+  constexpr bool TOK = ORD != 2;          // rows are written
+  constexpr bool TY = LAB && TOK;         // ... with their type tokens
   extern __shared__ __align__(16) unsigned char smem[];
   const int lane = lane_id();
   const bool is0 = lane == 0;
@@ -248,7 +257,7 @@ __global__ void __launch_bounds__(64) sent_large_kernel(const LargeArgs a) {
     auto flush = [&]() {
       wave_sync();
       const int count = pos - wbase;
-      for (int i = lane; i < count; i += kWave) {
+      for (int i = lane; TOK && i < count; i += kWave) {
         const int q = wbase + i;
         if (q < cap) {
           int t = win[i];
@@ -282,7 +291,7 @@ __global__ void __launch_bounds__(64) sent_large_kernel(const LargeArgs a) {
         }
         atomicOr(vscr + (kw >> 5), 1u << (kw & 31));
         klo = min(klo, kw); khi = max(khi, kw);
-        if (LAB) amin(reinterpret_cast<unsigned *>(key + kw), ((unsigned)dir << 31) | (unsigned)p);
+        if (TY) amin(reinterpret_cast<unsigned *>(key + kw), ((unsigned)dir << 31) | (unsigned)p);
       });
       cntv = wave_sum(cntv); dead = wave_sum(dead); klo = wave_min(klo); khi = wave_max(khi);
       nlive -= dead;
@@ -298,7 +307,7 @@ __global__ void __launch_bounds__(64) sent_large_kernel(const LargeArgs a) {
       {
         const int o = pos - wbase;
         if (LAB) {
-          const int ty = node_off + a.g.nattr[nb0 + v];
+          const int ty = TY ? node_off + a.g.nattr[nb0 + v] : 0;
           if (pred >= 0) {
             if (lane < 3) win[o + lane] = lane == 0 ? et : lane == 1 ? idx_off + kv : ty;
             pos += 3;
@@ -328,7 +337,7 @@ __global__ void __launch_bounds__(64) sent_large_kernel(const LargeArgs a) {
             if (lane < 32 && ((wd >> lane) & 1u)) {
               const int kk = (w0 + L) * 32 + lane;
               const int q = pos - wbase + per * __popc(wd & ((1u << lane) - 1u));
-              if (LAB) {
+              if (TY) {
                 const unsigned kx = (unsigned)aload(key + kk);
                 astore(key + kk, -1);
                 const int ty = kx == 0xFFFFFFFFu ? 0 : (int)a.g.eattr[e0 + (int)(kx & 0x7FFFFFFFu)];
@@ -372,7 +381,7 @@ __global__ void __launch_bounds__(64) sent_large_kernel(const LargeArgs a) {
             wave_sync();
             if ((unsigned)nxt >= (unsigned)n) break;     // (never: c counts the very set the pick selects from)
             int et = 0;
-            if (LAB) {   // first listed cur -> nxt, else first listed nxt -> cur
+            if (TY) {   // first listed cur -> nxt, else first listed nxt -> cur
               unsigned kx = 0xFFFFFFFFu;
               for_entries(cur, [&](bool valid, int w, int dir, int p) {
                 if (valid && w == nxt) kx = min(kx, ((unsigned)dir << 31) | (unsigned)p);
@@ -414,6 +423,18 @@ __global__ void __launch_bounds__(64) sent_large_kernel(const LargeArgs a) {
     }
     emit1(GTOK_SENT_EOS);
     flush();
+
+    if (ORD) {   // the visit order: the wave's table as it stands, 0xFFFF (never visited) widened to -1; nodes the batch's max_nodes
+                 // clamped away were never visited either.  Coalesced 32-bit vector stores inside the graph's own slice of the epoch's block.
+      wave_sync();
+      int32_t *ord = a.visit_index + (int64_t)(gv / G) * a.order_stride + nb0;
+      const int nout = nb0 < 0 ? 0 : (int)max((int64_t)0, min((int64_t)nfull, a.order_stride - nb0));
+      for (int i = lane; i < nout; i += kWave) {
+        const int k = i < n ? (int)vidx[i] : 0xFFFF;
+        ord[i] = k == 0xFFFF ? -1 : k;
+      }
+    }
+    if (!TOK) continue;
 
     // ---- row end: query ids (original node ids, not remapped), pad tail, true length
     const int ltrail = min(pos, lim);
@@ -460,18 +481,18 @@ extern "C" int64_t gtok_sent_large_workspace(int32_t max_nodes, int32_t max_edge
   return waves * large_slice(max_nodes > 0 ? max_nodes : 1, max_edges > 0 ? max_edges : 1).bytes;
 }
 
-extern "C" int gtok_sent_large(const gtok_csr *g, const gtok_sent_params *p, int32_t *out_ids, int32_t ld, int32_t *out_len,
-                               void *workspace, int64_t workspace_bytes, void *stream) {
-  gtok::DeviceScope device_scope((hipStream_t)stream);   // the stream's device, not the thread's current one
-  if (!device_scope.ok()) return GTOK_E_NO_DEVICE;
-  if (!g || !p || ld <= 0 || g->num_graphs < 0 || g->max_nodes < 0 || g->max_edges < 0) return GTOK_E_INVAL;
-  if (g->num_graphs == 0) return GTOK_OK;   // an empty batch is a no-op
-  if (!out_ids || !out_len) return GTOK_E_INVAL;
+// the argument rules the two entry points share (include/gtok.h); `rows`: out_ids / out_len are used.  GTOK_OK, a GTOK_E_* code,
+// or 1: an empty batch, nothing to do.  Pure host arithmetic: no device is asked for anything.
+static int large_check(const gtok_csr *g, const gtok_sent_params *p, bool rows, const int32_t *out_ids, int32_t ld, const int32_t *out_len,
+                       const void *workspace, int64_t workspace_bytes) {
+  if (!g || !p || (rows && ld <= 0) || g->num_graphs < 0 || g->max_nodes < 0 || g->max_edges < 0) return GTOK_E_INVAL;
+  if (g->num_graphs == 0) return 1;   // an empty batch is a no-op
+  if (rows && (!out_ids || !out_len)) return GTOK_E_INVAL;
   if (!g->node_ptr || !g->edge_ptr || !g->rowptr || (g->max_edges > 0 && !g->col)) return GTOK_E_INVAL;
   if (g->graph_ids || g->unit_ptr || g->unit_info) return GTOK_E_INVAL;      // a batch in dataset order only
   if (p->max_len < 0 || p->max_num_nodes < 0 || p->epoch_count < 0 || p->reserved != 0) return GTOK_E_INVAL;
   if (p->flags & ~(GTOK_SENT_NO_PAD | GTOK_SENT_U16)) return GTOK_E_INVAL;   // (GTOK_SENT_PACK_ONLY / _PACK_U8: gtok_sent_packed's)
-  const bool u16 = (p->flags & GTOK_SENT_U16) != 0;
+  const bool u16 = rows && (p->flags & GTOK_SENT_U16) != 0;
   if (u16 && (p->pad_id < 0 || p->pad_id > 65535)) return GTOK_E_INVAL;
   const int K = p->epoch_count > 1 ? p->epoch_count : 1;
   if ((int64_t)g->num_graphs * K > 0x7FFFFFFF / 2) return GTOK_E_TOO_LARGE;  // rows of the [K, G, ld] slab are counted in 32 bits
@@ -479,11 +500,17 @@ extern "C" int gtok_sent_large(const gtok_csr *g, const gtok_sent_params *p, int
   if (g->max_nodes > GTOK_SENT_LARGE_MAX_NODES) return GTOK_E_TOO_LARGE;
   // gtok_sent's id-space rule: every id of the row must fit 16 bits
   if (u16 && (int64_t)GTOK_SENT_IDX_OFFSET + p->max_num_nodes + p->num_node_types + 512 > 65535) return GTOK_E_TOO_LARGE;
-  const int pairs = g->num_graphs * K;
-  const int64_t need = gtok_sent_large_workspace(g->max_nodes, g->max_edges, pairs);
+  const int64_t need = gtok_sent_large_workspace(g->max_nodes, g->max_edges, (int64_t)g->num_graphs * K);
   if (need < 0) return (int)need;
   if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15u) || workspace_bytes < need) return GTOK_E_INVAL;
+  return GTOK_OK;
+}
 
+// ord: 0 = gtok_sent_large, 1 = rows and order, 2 = order only (LargeArgs.out / ld are not used)
+static int large_launch(const gtok_csr *g, const gtok_sent_params *p, int32_t *out_ids, int32_t ld, int32_t *out_len, int ord,
+                        int32_t *visit_index, int64_t order_stride, void *workspace, hipStream_t stream) {
+  const int K = p->epoch_count > 1 ? p->epoch_count : 1;
+  const int pairs = g->num_graphs * K;
   LargeArgs a;
   a.g = *g; a.p = *p; a.out = out_ids; a.ld = ld; a.out_len = out_len;
   a.maxn = g->max_nodes; a.maxe = g->max_edges;
@@ -493,11 +520,40 @@ extern "C" int gtok_sent_large(const gtok_csr *g, const gtok_sent_params *p, int
   a.off_key = s.key; a.off_inptr = s.inptr; a.off_insrc = s.insrc; a.off_inpos = s.inpos;
   a.nw = ((tabn + 31) / 32 + 3) & ~3;                      // (whole 16-byte pieces: the window behind the sets stays aligned)
   a.pairs = pairs;
+  a.visit_index = visit_index; a.order_stride = order_stride;
   // LDS by the batch's max_nodes: four sets, the window, 16 bits per node - 43 KB at 16,384 nodes (three waves per CU)
   const size_t lds = (size_t)4 * a.nw * 4 + (size_t)kLargeWin * 4 + (((size_t)tabn * 2 + 15) & ~(size_t)15);
   const int nb = pairs < GTOK_SENT_LARGE_WAVES ? pairs : GTOK_SENT_LARGE_WAVES;
   typedef void (*Kern)(const LargeArgs);
-  const Kern kern = p->labeled ? (Kern)sent_large_kernel<true> : (Kern)sent_large_kernel<false>;
-  hipLaunchKernelGGL(kern, dim3(nb), dim3(64), lds, (hipStream_t)stream, a);
+  const bool lab = p->labeled != 0;
+  const Kern kern = ord == 0 ? (lab ? (Kern)sent_large_kernel<true> : (Kern)sent_large_kernel<false>)
+                  : ord == 1 ? (lab ? (Kern)sent_large_kernel<true, 1> : (Kern)sent_large_kernel<false, 1>)
+                             : (lab ? (Kern)sent_large_kernel<true, 2> : (Kern)sent_large_kernel<false, 2>);
+  hipLaunchKernelGGL(kern, dim3(nb), dim3(64), lds, stream, a);
   return hipGetLastError() == hipSuccess ? GTOK_OK : GTOK_E_LAUNCH;
+}
+
+extern "C" int gtok_sent_large(const gtok_csr *g, const gtok_sent_params *p, int32_t *out_ids, int32_t ld, int32_t *out_len,
+                               void *workspace, int64_t workspace_bytes, void *stream) {
+  gtok::DeviceScope device_scope((hipStream_t)stream);   // the stream's device, not the thread's current one
+  if (!device_scope.ok()) return GTOK_E_NO_DEVICE;
+  const int c = large_check(g, p, true, out_ids, ld, out_len, workspace, workspace_bytes);
+  if (c) return c < 0 ? c : GTOK_OK;
+  return large_launch(g, p, out_ids, ld, out_len, 0, nullptr, 0, workspace, (hipStream_t)stream);
+}
+
+extern "C" int gtok_sent_large_order(const gtok_csr *g, const gtok_sent_params *p, int32_t *out_ids, int32_t ld, int32_t *out_len,
+                                     int32_t *visit_index, int64_t order_stride, void *workspace, int64_t workspace_bytes, void *stream) {
+  // every argument error before any device is asked for
+  if ((out_ids == nullptr) != (out_len == nullptr)) return GTOK_E_INVAL;
+  const bool rows = out_ids != nullptr;
+  if (!visit_index || order_stride < 0) return GTOK_E_INVAL;
+  const int c = large_check(g, p, rows, out_ids, ld, out_len, workspace, workspace_bytes);
+  if (c) return c < 0 ? c : GTOK_OK;
+  gtok::DeviceScope device_scope((hipStream_t)stream);
+  if (!device_scope.ok()) return GTOK_E_NO_DEVICE;
+  if (rows) return large_launch(g, p, out_ids, ld, out_len, 1, visit_index, order_stride, workspace, (hipStream_t)stream);
+  gtok_sent_params q = *p;              // order only: nothing of a row is written, whatever the row flags say
+  q.flags = GTOK_SENT_NO_PAD; q.query = nullptr;
+  return large_launch(g, &q, nullptr, 0, nullptr, 2, visit_index, order_stride, workspace, (hipStream_t)stream);
 }

@@ -602,6 +602,61 @@ def sent_large(batch: GraphBatch, max_num_nodes: int, max_len: int, seed: int, e
     return ids.view(*shape, ld), ln.view(shape)
 
 
+def _need_order() -> None:
+    """gtok_sent_large_order / gtok_csr_relabel came without an ABI version step: a library loaded through GTOK_LIB may lack them."""
+    if not all(hasattr(lib(), n) for n in _lib.ORDER_SYMBOLS):
+        raise _lib.GtokError(f"{_lib.LIB_PATH} has no gtok_sent_large_order / gtok_csr_relabel: it was built before they were added")
+
+
+def sent_order(batch: GraphBatch, max_len: int, seed: int, epoch: int = 0, epochs: int = 1, graph_base: int = 0, with_rows: bool = False,
+               max_num_nodes: Optional[int] = None, labeled: bool = False, num_node_types: int = 0, num_edge_types: int = 0,
+               remap_zinc: bool = False, pad_id: int = SENT_PAD, query: Optional[torch.Tensor] = None, ld: Optional[int] = None,
+               pad: bool = True, u16: bool = False, workspace: Optional[torch.Tensor] = None):
+    """gtok_sent_large_order: the visit order of the SENT walks of (seed, epoch .. epoch + K - 1, graph_base + g) - visit_index int32
+    [K, N_total]: visit_index[e, node_ptr[g] + u] = k when node u of graph g was the k-th node first visited (position token 6 + k),
+    -1 when the walk stopped (max_len) before it got there.  It is the order of the rows of ops.sent as well (every SENT kernel emits
+    the same tokens), for any batch in dataset order with graphs of up to _lib.SENT_LARGE_MAX_NODES nodes.  Pass the max_len and
+    labeled the rows were written with (they decide where a cut walk stops); nothing else of the row format matters.
+    with_rows=True: -> (visit_index, ids, len), the rows ops.sent_large returns (its keywords), from the same launch.
+    workspace: as ops.sent_large."""
+    _need_gpu(batch.col, "sent_order")
+    _need_order()
+    dev = batch.device
+    K = max(1, int(epochs))
+    G, N = batch.num_graphs, batch.num_nodes_total
+    if max_num_nodes is None:
+        max_num_nodes = batch.max_nodes
+    vis = torch.empty((K, N), dtype=torch.int32, device=dev)
+    ids = ln = None
+    flags = 0
+    if with_rows:
+        if query is not None:
+            query = query.to(dev, dtype=torch.int32).contiguous()
+            if tuple(query.shape) != (G, 2):
+                raise ValueError("query must be [G, 2] (query_u, query_v)")
+        if ld is None:
+            ld = sent_safe_ld(batch, labeled, max_len, query is not None)
+        ids, _, ln = _sent_out(None, True, K, G, ld, u16, dev)
+        flags = (0 if pad else _lib.SENT_NO_PAD) | (_lib.SENT_U16 if u16 else 0)
+    p = _sent_params(max_num_nodes, max_len, labeled, num_node_types, num_edge_types, remap_zinc, pad_id, flags, seed, epoch, graph_base,
+                     query if with_rows else None, K)
+    cs = batch.c_struct()
+    need = int(lib().gtok_sent_large_workspace(batch.max_nodes, batch.max_edges, G * K))
+    if need < 0:
+        check(need, "gtok_sent_large_workspace")
+    ws = workspace if workspace is not None else _large_workspace(dev, need)
+    if ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.device != torch.device(dev):
+        raise ValueError("workspace: a contiguous uint8 tensor on the batch's device")
+    spare = vis if N else torch.empty(1, dtype=torch.int32, device=dev)      # (the library wants an address: an empty tensor has none)
+    check(lib().gtok_sent_large_order(ctypes.byref(cs), ctypes.byref(p), None if ids is None else ids.data_ptr(), int(ld or 0),
+                                      None if ln is None else ln.data_ptr(), spare.data_ptr(), N, ws.data_ptr(), ws.numel(), _stream(dev)),
+          "gtok_sent_large_order")
+    if not with_rows:
+        return vis
+    shape = (K, G) if K > 1 else (G,)
+    return vis, ids.view(*shape, ld), ln.view(shape)
+
+
 def _sent_params(max_num_nodes: int, max_len: int, labeled: bool, num_node_types: int, num_edge_types: int, remap_zinc: bool,
                  pad_id: int = SENT_PAD, flags: int = 0, seed: int = 0, epoch: int = 0, graph_base: int = 0,
                  query: Optional[torch.Tensor] = None, epochs: int = 1) -> GtokSentParams:
@@ -1000,6 +1055,124 @@ def ibtt_decode_csr(ids: torch.Tensor, ln: torch.Tensor, grammar, inv: torch.Ten
             b.flags |= _lib.CSR_SIMPLE_SYMMETRIC
         b.checked = True
     return (b, status, sizes[3]) if synth else (b, status)
+
+
+# ------------------------------------------------------------------------------------------------
+# a batched CSR in another numbering (include/gtok.h: gtok_csr_relabel), graph equality
+# ------------------------------------------------------------------------------------------------
+_RELABEL_WS = {}
+
+
+def _relabel_launch(batch: GraphBatch, old_of_new: torch.Tensor, target_node_ptr: torch.Tensor, target_max_nodes: int, total: int) -> dict:
+    """gtok_csr_relabel on the current stream into fresh arrays: -> dict(rowptr, col, eorder, nattr, eattr, info, status); no host read."""
+    _need_gpu(batch.col, "csr_relabel")
+    _need_order()
+    dev, G, E = batch.device, batch.num_graphs, batch.num_edges_total
+    total = int(total)
+    if old_of_new.dtype != torch.int32 or old_of_new.dim() != 1 or not old_of_new.is_contiguous() or old_of_new.device != dev \
+            or int(old_of_new.numel()) != total:
+        raise ValueError("csr_relabel: old_of_new must be a contiguous int32 vector of one entry per target node on the batch's device")
+    if target_node_ptr.dtype != torch.int32 or target_node_ptr.numel() != G + 1 or not target_node_ptr.is_contiguous() or target_node_ptr.device != dev:
+        raise ValueError("csr_relabel: target_node_ptr must be a contiguous int32 [G + 1] on the batch's device")
+    if total < 0 or total + G >= 2 ** 31:
+        raise ValueError("csr_relabel: totals out of range (a batch holds fewer than 2^31 nodes + graphs; shard it)")
+    has_n, has_e = batch.nattr is not None, batch.eattr is not None
+    new = lambda n, dt: torch.empty(n + 1, dtype=dt, device=dev)       # (one spare element: an empty tensor has no address)
+    full = dict(rowptr=new(total + G, torch.int32), col=new(E, torch.int32), eorder=new(E, torch.int32),
+                nattr=new(total, torch.uint8) if has_n else None, eattr=new(E, torch.uint8) if has_e else None, info=new(8, torch.int32),
+                status=new(G, torch.int32))
+    o = {k: None if t is None else t[:-1] for k, t in full.items()}
+    if G == 0:
+        o["info"].zero_()
+        return o
+    need = int(lib().gtok_csr_relabel_workspace(G, E))
+    if need < 0:
+        check(need, "gtok_csr_relabel_workspace")
+    key = torch.device(dev).index or 0
+    ws = _RELABEL_WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _RELABEL_WS[key] = torch.empty(max(16, need), dtype=torch.uint8, device=dev)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    cout = _lib.GtokCsrBuilt(None, None, ptr(full["rowptr"]), ptr(full["col"]), ptr(full["eorder"]), ptr(full["nattr"]), ptr(full["eattr"]),
+                             ptr(full["info"]))
+    cs = batch.c_struct()
+    oon = old_of_new if total else torch.empty(1, dtype=torch.int32, device=dev)
+    check(lib().gtok_csr_relabel(ctypes.byref(cs), target_node_ptr.data_ptr(), int(target_max_nodes), oon.data_ptr(), ctypes.byref(cout),
+                                 full["status"].data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)), "gtok_csr_relabel")
+    return o
+
+
+def csr_relabel(batch: GraphBatch, old_of_new: torch.Tensor, target_node_ptr: Optional[torch.Tensor] = None,
+                target_max_nodes: Optional[int] = None) -> Tuple[GraphBatch, torch.Tensor]:
+    """gtok_csr_relabel: `batch` renumbered through a per-graph node map -> (GraphBatch, status int32 [G]).  old_of_new int32
+    [target total]: the old id of target node t of graph g at target_node_ptr[g] + t, anything outside [0, N_old) = absent (such a
+    node comes out isolated, type 255) - a visit_index slice of ops.sent_order when `batch` was decoded from SENT rows.
+    target_node_ptr int32 [G + 1] (None: the batch's own node_ptr), target_max_nodes: a bound on the target node counts (None: read
+    from target_node_ptr, one host read).  Rows come out in ascending new column, duplicates in input order; eorder = every entry's
+    local index in the old graph's entry list.  status: 0 built, 2 built but not simple (a duplicate or a self loop), 1 skipped (the
+    map names an old node twice or not at all, damaged arrays: the graph's arrays are undefined).  One read-back (`info`): the
+    returned batch carries its maxima, as ops.sent_decode_csr sets them."""
+    dev = batch.device
+    old_of_new = old_of_new.to(dev, dtype=torch.int32).contiguous().reshape(-1)
+    if target_node_ptr is None:
+        target_node_ptr = batch.node_ptr
+        if target_max_nodes is None:
+            target_max_nodes = batch.max_nodes
+    else:
+        target_node_ptr = target_node_ptr.to(dev, dtype=torch.int32).contiguous()
+        if target_max_nodes is None:
+            target_max_nodes = int((target_node_ptr[1:] - target_node_ptr[:-1]).max()) if batch.num_graphs else 0
+    total = int(old_of_new.numel())
+    o = _relabel_launch(batch, old_of_new, target_node_ptr, target_max_nodes, total)
+    v = o["info"].tolist()
+    b = GraphBatch(batch.num_graphs, v[2], v[3], target_node_ptr, batch.edge_ptr, o["rowptr"], o["col"], o["eorder"], o["nattr"], o["eattr"],
+                   0, v[4], v[5], v[1])
+    if batch.num_graphs and batch.num_edges_total and v[0] == 0 and v[6] == 0 and (batch.flags & _lib.CSR_SIMPLE_SYMMETRIC):
+        b.flags |= _lib.CSR_SIMPLE_SYMMETRIC          # (a renumbering keeps a verified simple symmetric batch simple and symmetric)
+        b.checked = batch.checked
+    return b, o["status"]
+
+
+def graphs_equal(a: GraphBatch, b: GraphBatch) -> torch.Tensor:
+    """bool [G]: graph g of `a` and of `b` have the same node and entry counts and equal rowptr / col / nattr / eattr slices (an
+    attribute array only one of the two has: unequal wherever a node / an entry exists).  Two graphs in one numbering and in
+    ops.csr_relabel's canonical entry order are the same graph iff this says so.  Torch segment reductions on the device; the result stays there."""
+    if a.num_graphs != b.num_graphs:
+        raise ValueError("graphs_equal: batches of different graph counts")
+    dev, G = a.device, a.num_graphs
+    if b.device != dev:
+        raise ValueError("graphs_equal: batches on different devices")
+    na, nb_ = a.node_ptr[1:] - a.node_ptr[:-1], b.node_ptr[1:] - b.node_ptr[:-1]
+    ea, eb = a.edge_ptr[1:] - a.edge_ptr[:-1], b.edge_ptr[1:] - b.edge_ptr[:-1]
+    same = (na == nb_) & (ea == eb)
+    if G == 0:
+        return same
+    gid = torch.arange(G, device=dev)
+    n64, e64 = na.to(torch.int64), ea.to(torch.int64)
+
+    def segments(x, y, counts_a, ptr_a, ptr_b, extra):
+        """per graph: no element of x's slice differs from y's (compared where the counts agree: indices built from a's pointers)"""
+        cnt = torch.where(same, counts_a + extra, torch.zeros_like(counts_a))
+        seg = torch.repeat_interleave(gid, cnt)
+        start = torch.cumsum(cnt, 0) - cnt
+        local = torch.arange(seg.numel(), device=dev) - start[seg]
+        ia = ptr_a.to(torch.int64)[seg] + (seg if extra else 0) + local
+        ib = ptr_b.to(torch.int64)[seg] + (seg if extra else 0) + local
+        diff = (x[ia] != y[ib]).to(torch.int32)
+        bad = torch.zeros(G, dtype=torch.int32, device=dev)
+        bad.index_add_(0, seg, diff)
+        return bad == 0
+
+    same = same & segments(a.rowptr, b.rowptr, n64, a.node_ptr, b.node_ptr, 1)
+    same = same & segments(a.col, b.col, e64, a.edge_ptr, b.edge_ptr, 0)
+    for xa, xb, cnt, pa, pb in ((a.nattr, b.nattr, n64, a.node_ptr, b.node_ptr), (a.eattr, b.eattr, e64, a.edge_ptr, b.edge_ptr)):
+        if xa is None and xb is None:
+            continue
+        if xa is None or xb is None:
+            same = same & (cnt == 0)
+        else:
+            same = same & segments(xa, xb, cnt, pa, pb, 0)
+    return same
 
 
 def remap_zinc(ids: torch.Tensor, ln: torch.Tensor, idx_offset: int, node_idx_offset: int,

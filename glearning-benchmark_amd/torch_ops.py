@@ -577,6 +577,47 @@ def _(ids, lens, grammar, inv, max_num_nodes, node_ptr, edge_ptr, total_nodes, t
             e(total_nodes if typed else 0, torch.uint8), e(total_entries if typed else 0, torch.uint8), e(8, torch.int32))
 
 
+@torch.library.custom_op("gtok::sent_order", mutates_args=(), device_types="cuda")
+def sent_order(node_ptr: Tensor, edge_ptr: Tensor, rowptr: Tensor, col: Tensor, nattr: Optional[Tensor], eattr: Optional[Tensor],
+               max_nodes: int, max_edges: int, total_nodes: int, max_num_nodes: int, max_len: int, seed: int, epoch: int, epochs: int,
+               labeled: bool, num_node_types: int, graph_base: int) -> Tensor:
+    """gtok_sent_large_order, order only: visit_index int32 [max(epochs, 1), total_nodes] of the walks gtok::sent / gtok::sent_large
+    run for the same (seed, epoch, graph_base) - -1 where a walk cut at max_len never got.  total_nodes = node_ptr[-1] as an int (the
+    shape is static); the batch is in dataset order."""
+    b = GraphBatch(int(node_ptr.numel()) - 1, max_nodes, max_edges, node_ptr, edge_ptr, rowptr, col, None, nattr, eattr)
+    if b.num_nodes_total != total_nodes:
+        raise ValueError("gtok::sent_order: total_nodes is the batch's node total (rowptr holds total_nodes + G entries)")
+    return _ops.sent_order(b, max_len, seed, epoch, epochs=epochs, graph_base=graph_base, max_num_nodes=max_num_nodes, labeled=labeled,
+                           num_node_types=num_node_types)
+
+
+@sent_order.register_fake
+def _(node_ptr, edge_ptr, rowptr, col, nattr, eattr, max_nodes, max_edges, total_nodes, max_num_nodes, max_len, seed, epoch, epochs, labeled,
+      num_node_types, graph_base):
+    return node_ptr.new_empty((max(1, epochs), total_nodes), dtype=torch.int32)
+
+
+@torch.library.custom_op("gtok::csr_relabel", mutates_args=(), device_types="cuda")
+def csr_relabel(node_ptr: Tensor, edge_ptr: Tensor, rowptr: Tensor, col: Tensor, nattr: Optional[Tensor], eattr: Optional[Tensor],
+                max_nodes: int, max_edges: int, old_of_new: Tensor, target_node_ptr: Tensor,
+                target_max_nodes: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """gtok_csr_relabel: the batch renumbered through old_of_new int32 [target total] (target_node_ptr int32 [G + 1]) -> (rowptr int32
+    [target total + G], col int32 [E], eorder int32 [E], nattr uint8 [target total], eattr uint8 [E] (empty when the batch has none),
+    info int32 [8], status int32 [G]) (include/gtok.h).  Nothing is read back: every shape follows from the inputs'."""
+    b = GraphBatch(int(node_ptr.numel()) - 1, max_nodes, max_edges, node_ptr, edge_ptr, rowptr, col, None, nattr, eattr)
+    o = _ops._relabel_launch(b, old_of_new, target_node_ptr, target_max_nodes, int(old_of_new.numel()))
+    e = lambda t: torch.empty(0, dtype=torch.uint8, device=col.device) if t is None else t
+    return o["rowptr"], o["col"], o["eorder"], e(o["nattr"]), e(o["eattr"]), o["info"], o["status"]
+
+
+@csr_relabel.register_fake
+def _(node_ptr, edge_ptr, rowptr, col, nattr, eattr, max_nodes, max_edges, old_of_new, target_node_ptr, target_max_nodes):
+    G, E, T = node_ptr.shape[0] - 1, col.shape[0], old_of_new.shape[0]
+    e = lambda n, dt: col.new_empty((n,), dtype=dt)
+    return (e(T + G, torch.int32), e(E, torch.int32), e(E, torch.int32), e(T if nattr is not None else 0, torch.uint8),
+            e(E if eattr is not None else 0, torch.uint8), e(8, torch.int32), e(G, torch.int32))
+
+
 # ---- packed (ragged) rows: include/gtok.h, "packed rows" -----------------------------------------------------------------
 @torch.library.custom_op("gtok::row_offsets", mutates_args=(), device_types="cuda")
 def row_offsets(lens: Tensor, ld: int, align: int) -> Tensor:

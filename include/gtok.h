@@ -429,6 +429,28 @@ int64_t gtok_sent_large_workspace(int32_t max_nodes, int32_t max_edges, int64_t 
 int gtok_sent_large(const gtok_csr *g, const gtok_sent_params *p, int32_t *out_ids, int32_t ld, int32_t *out_len,
                     void *workspace, int64_t workspace_bytes, void *stream);
 
+/* gtok_sent_large's walk that also - or only - exports its VISIT ORDER: what maps a decoded SENT graph (visit-index space,
+ * gtok_sent_decode_csr) back to the input's node ids.
+ *   visit_index[e * order_stride + node_ptr[g] + u] = k: node u of graph g was the k-th node first visited by the walk of epoch
+ *   p->epoch + e; the position token GTOK_SENT_IDX_OFFSET + k names it.  -1: the walk had not visited u when it stopped (a row cut
+ *   at max_len; a node beyond a clamped max_nodes).
+ * The walk stops at the first loop test with pos >= max_len, so a visit that BEGAN below max_len is recorded even when its position
+ * token falls just behind the cut: a reader that pairs the order with a decoded, cut row treats an index >= the decoded node count
+ * as absent (gtok_csr_relabel does).  order_stride (elements) >= the batch's node total node_ptr[G], which the host knows; the array
+ * holds K * order_stride int32, K = max(epoch_count, 1); elements of a block beyond the node total are not touched.
+ * Every SENT kernel emits the same tokens for the same (seed, epoch, graph_base + g), so this is the order of the rows of gtok_sent
+ * and gtok_sent_packed as well, whichever kernel wrote them: any batch in dataset order is accepted, small graphs included.  The
+ * visit index of a node depends on (seed, epoch, graph_base + g) and the edge list only - not on labeled, remap_zinc, query or the
+ * row width; how far a cut walk got depends on max_len and, through the tokens a visit costs, on labeled: pass the max_len and
+ * labeled the rows were written with.
+ * out_ids / out_len: both set - rows and lengths bit for bit gtok_sent_large's, from the same launch; both NULL - an order-only call:
+ * no token is stored, ld, query, GTOK_SENT_U16 and GTOK_SENT_NO_PAD are ignored; one of the two NULL: GTOK_E_INVAL.  Everything else -
+ * batch rules, errors, the workspace (gtok_sent_large_workspace), one wave per (graph, epoch) pair, at most GTOK_SENT_LARGE_WAVES
+ * waves - is gtok_sent_large's; also GTOK_E_INVAL: visit_index NULL, order_stride < 0.  Argument errors are answered before any
+ * device is asked for.  The export is one coalesced 32-bit store per node when a walk ends.  (Added without an ABI version step.)  */
+int gtok_sent_large_order(const gtok_csr *g, const gtok_sent_params *p, int32_t *out_ids, int32_t ld, int32_t *out_len,
+                          int32_t *visit_index, int64_t order_stride, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* gtok_sent whose walk ALSO appends every row to a packed buffer (ABI v6): the payload of the compact all-gather and of the
  * per-epoch D2H copy without a second pass over the rows.  `packed` holds `capacity` ids of the slab's width (16-bit with
  * GTOK_SENT_U16, else 32-bit; one byte per id with GTOK_SENT_PACK_U8, below).  The library cuts it into R <= GTOK_PACK_REGIONS equal regions of (capacity / R rounded down to a
@@ -757,6 +779,44 @@ int gtok_ibtt_decode_sizes(const void *ids, int32_t elem_bytes, const int64_t *r
 int gtok_ibtt_decode_csr(const void *ids, int32_t elem_bytes, const int64_t *row_start, int32_t ld, const int32_t *len,
                          int32_t num_rows, int32_t grammar, const int32_t *inv, int32_t inv_len, int32_t max_num_nodes,
                          const gtok_csr_built *out, void *stream);
+
+/* ---- gtok_csr_relabel: a batched CSR renumbered through a per-graph node map, in a canonical entry order ---------------------
+ * g: the graphs to renumber ("old" ids), dataset order.  target_node_ptr int32 [G + 1]: node_ptr of the TARGET numbering (NULL =
+ * g->node_ptr); target_max_nodes: a host-known bound on the target node counts.  old_of_new int32 [target_node_ptr[G]]: the old id
+ * of target node t of graph g at target_node_ptr[g] + t; a value outside [0, N_old) = absent.  It is exactly a visit_index slice
+ * (gtok_sent_large_order) when g is a decoded batch and the target is the batch that was tokenized.
+ * Per graph (N_old = g's node count, N_t = the target's, E_g unchanged): the map must name every old node exactly once (N_old <=
+ * N_t; the entries of old_of_new inside [0, N_old) are a bijection onto it).  Target nodes with an absent entry become isolated
+ * nodes of type 255.  Row t of the output lists old row old_of_new[t]'s entries with their columns renumbered, in ascending new
+ * column; entries of equal column (duplicates) keep their input order (a stable sort); a self loop stays a self loop.  Two graphs
+ * are equal iff their relabelled arrays are, provided neither lists an edge twice.
+ * out: rowptr int32 [target total + G] (gtok_csr's layout over the target's node_ptr), col int32 [E] the renumbered columns, eorder
+ * int32 [E] always written: the entry's local index in the old graph's entry list (a gather map for whatever else the caller keeps
+ * per entry), nattr uint8 [target total] / eattr uint8 [E] only when g has them (they follow their node / entry); out->node_ptr /
+ * out->edge_ptr are not touched (they would equal target_node_ptr / g->edge_ptr).
+ * status int32 [G]: 0 built; 2 built, but some row holds a duplicate or a self loop (the graph is not simple); 1 skipped: the map
+ * is not such a bijection, N_old > N_t, N_t > target_max_nodes (or N_old > g->max_nodes, E_g > g->max_edges: the other host-known
+ * bounds), a slice outside the totals of its pointer array, a column outside [0, N_old), row pointers that decrease or do not run
+ * from 0 to E_g.  A skipped graph's arrays are undefined; nothing is ever written outside the graph's own slices, whatever the
+ * inputs hold, and nothing is read through an index that was not range-checked first - given that the arrays are as long as their
+ * pointer arrays say.
+ * out->info int32 [8], zeroed by the call: [0] skipped graphs, [1] max_degree, [2] max_nodes (target counts), [3] max_edges of the
+ * built graphs, [4] chunk_nodes, [5] chunk_edges (gtok_csr_from_coo's meaning: maxima over aligned groups of 64 graphs of the
+ * built graphs' summed counts), [6] status-2 graphs, [7] 0.
+ * One wave per graph; the old -> new table lives in LDS, 16 bits per node (36 KB per wave at 16,384 nodes with the set the
+ * bijection is checked on).  Rows of up to 64 entries are ranked in registers; longer ones through an N-bit set with popcount
+ * ranks (rows with duplicates: a stable count, d steps per 64 entries): a simple graph costs O(N + E) lane steps plus N / 2,048
+ * wave steps per row of more than 64 entries.
+ * workspace: gtok_csr_relabel_workspace(G, E) bytes of device memory (pure host arithmetic; a multiple of 16, 0 for an empty batch;
+ * GTOK_E_INVAL for a negative argument), 16-byte aligned, free again when the stream has run the call.
+ * Errors, all before any device is asked for: GTOK_E_INVAL for null pointers, negative sizes, a reordered batch (graph_ids /
+ * unit_ptr set), g with attributes and out without, a misaligned or short workspace; GTOK_E_TOO_LARGE for target_max_nodes or
+ * g->max_nodes beyond GTOK_SENT_LARGE_MAX_NODES; num_graphs == 0 is a no-op.  The call only enqueues on `stream` (two memsets, two
+ * launches): no allocation, no host synchronisation, no library-owned counters - it can be captured into a hipGraph.  (Added
+ * without an ABI version step, like the decoders: no struct changes.)                                                         */
+int64_t gtok_csr_relabel_workspace(int32_t num_graphs, int64_t num_entries);
+int gtok_csr_relabel(const gtok_csr *g, const int32_t *target_node_ptr, int32_t target_max_nodes, const int32_t *old_of_new,
+                     const gtok_csr_built *out, int32_t *status, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* Which SENT kernel gtok_sent() will run for this batch ("sent_lane_kernel": lane per graph over the CSR, needs
  * GTOK_CSR_SIMPLE_SYMMETRIC, <= 64 nodes and a large batch; "sent_blane_kernel<W=..>": lane per graph over the
