@@ -12,9 +12,9 @@ _ROOT = os.path.dirname(_HERE)
 # GTOK_LIB: load another build of the same ABI (profiling builds of profiles/tools, e.g. -DGTOK_PHASE_TIMING)
 LIB_PATH = os.environ.get("GTOK_LIB") or os.path.join(_HERE, "csrc", "libgtok.so")
 SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("gtok_sent.hip", "gtok_sent_large.hip", "gtok_sent_decode.hip", "gtok_ibtt.hip", "gtok_ibtt_decode.hip", "gtok_csr_relabel.hip", "gtok_text.hip", "gtok_rows.hip", "gtok_csr.hip")]
-HEADERS = [os.path.join(_HERE, "csrc", "gtok_common.hpp"), os.path.join(_HERE, "csrc", "gtok_sent_blane.hpp"), os.path.join(_HERE, "csrc", "gtok_sent_reg.hpp"), os.path.join(_HERE, "csrc", "gtok_sent_lds.hpp"),
-           os.path.join(_HERE, "csrc", "gtok_sent_lane.hpp"), os.path.join(_HERE, "csrc", "gtok_sent_decode_args.hpp"), os.path.join(_HERE, "csrc", "gtok_ibtt_decode_args.hpp"), os.path.join(_HERE, "csrc", "gtok_csr_relabel_args.hpp"),
-           os.path.join(_ROOT, "include", "gtok.h")]
+HEADERS = [os.path.join(_HERE, "csrc", h) for h in ("gtok_common.hpp", "gtok_sent_blane.hpp", "gtok_sent_reg.hpp", "gtok_sent_lds.hpp", "gtok_sent_lane.hpp",
+                                                   "gtok_decode_args.hpp", "gtok_decode_csr.hpp", "gtok_csr_relabel_args.hpp")] \
+          + [os.path.join(_ROOT, "include", "gtok.h")]
 
 c_i32p = ctypes.POINTER(ctypes.c_int32)
 c_i64p = ctypes.POINTER(ctypes.c_int64)
@@ -153,6 +153,7 @@ OPTIONAL_SYMBOLS = ("gtok_sent_large_workspace", "gtok_sent_large")
 DECODE_CSR_SYMBOLS = ("gtok_sent_decode_sizes", "gtok_sent_decode_csr")     # likewise (ops.sent_decode_csr)
 IBTT_DECODE_SYMBOLS = ("gtok_ibtt_decode_sizes", "gtok_ibtt_decode_csr")    # likewise (ops.ibtt_decode_csr)
 ORDER_SYMBOLS = ("gtok_sent_large_order", "gtok_csr_relabel_workspace", "gtok_csr_relabel")   # likewise (ops.sent_order, ops.csr_relabel)
+_MAY_BE_MISSING = frozenset(OPTIONAL_SYMBOLS + DECODE_CSR_SYMBOLS + IBTT_DECODE_SYMBOLS + ORDER_SYMBOLS)
 IBTT_GRAMMAR_ZINC, IBTT_GRAMMAR_SYNTH = 0, 1                                # include/gtok.h: GTOK_IBTT_GRAMMAR_*
 
 ERRORS = {-1: "GTOK_E_INVAL", -2: "GTOK_E_TOO_LARGE", -3: "GTOK_E_LAUNCH", -4: "GTOK_E_NO_DEVICE", -5: "GTOK_E_GRAPH_SLOTS", -6: "GTOK_E_UNSUPPORTED"}
@@ -230,7 +231,7 @@ def lib() -> ctypes.CDLL:
         # (library_version() gates the inputs an older library would silently ignore: ops.sent)
         older_ok = bool(os.environ.get("GTOK_LIB")) and 3 <= h.gtok_version() < ABI_VERSION
         for name, (res, args) in SYMBOLS.items():
-            if (older_ok or name in OPTIONAL_SYMBOLS or name in DECODE_CSR_SYMBOLS or name in IBTT_DECODE_SYMBOLS or name in ORDER_SYMBOLS) and not hasattr(h, name):
+            if (older_ok or name in _MAY_BE_MISSING) and not hasattr(h, name):
                 continue
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args

@@ -369,6 +369,44 @@ __device__ __forceinline__ uint64_t uni(uint64_t v) {
   return ((uint64_t)hi << 32) | lo;
 }
 
+// Wave-uniform reads of the read-only graph pointers as SCALAR loads (constant address space): the
+// compiler will not prove invariance through the by-value argument struct on its own.
+typedef const int32_t __attribute__((address_space(4))) *kptr32;
+typedef const int64_t __attribute__((address_space(4))) *kptr64;
+__device__ __forceinline__ int sload(const int32_t *p, int64_t i) { return ((kptr32)(uintptr_t)p)[i]; }
+__device__ __forceinline__ int64_t sload(const int64_t *p, int64_t i) { return ((kptr64)(uintptr_t)p)[i]; }
+
+// Scan and reductions over the 64 lanes.  The reductions leave the result in every lane's VECTOR register: where a caller
+// needs it wave-uniform (loop control, an address), it writes uni(wave_max(x)).
+__device__ __forceinline__ int wave_incl_scan(int v) {
+  const int lane = lane_id();
+#pragma unroll
+  for (int o = 1; o < kWave; o <<= 1) {
+    const int t = __shfl_up(v, o);
+    if (lane >= o) v += t;
+  }
+  return v;
+}
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ __forceinline__ int wave_min(int v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v = min(v, __shfl_xor(v, o));
+  return v;
+}
+__device__ __forceinline__ int wave_max(int v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v = max(v, __shfl_xor(v, o));
+  return v;
+}
+// *p = max(*p, v) from one lane, the atomic skipped when it would change nothing
+__device__ __forceinline__ void info_max(int32_t *p, int v) {
+  if (v > __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p, v);
+}
+
 // k-th (0-based) set bit of a wave-uniform 64-bit word, ascending bit index:
 // every lane tests its own bit, one ballot + ffs picks the winner.
 __device__ __forceinline__ int kth_bit(uint64_t word, int k) {

@@ -24,16 +24,6 @@ namespace gtok {
 
 constexpr int kInfoViol = 0, kInfoMaxDeg = 1, kInfoMaxN = 2, kInfoMaxE = 3, kInfoUnits = 4, kInfoChunkN = 5, kInfoChunkE = 6;
 
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = max(v, __shfl_xor(v, o));
-  return v;
-}
-
-__device__ __forceinline__ void raise_max(int32_t *p, int v) {
-  if (v > __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p, v);
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // structure check + per-graph sort key.  One wave per 64 consecutive graphs; lanes stride over the group's ROWS (the
 // rows of a group are contiguous in rowptr, so the loads coalesce), a row's graph is found by bisection over the group's
@@ -189,9 +179,9 @@ __global__ void __launch_bounds__(256) csr_scan_kernel(const CsrScanArgs a) {
     // (four words of one line, 3.9 k waves: every wave's atomics in a row cost 130 us of ZINC-full's 144 - one word takes ~88
     // atomics per microsecond; a maximum that is already there needs none)
     if (vs) atomicAdd(a.info + kInfoViol, vs);
-    raise_max(a.info + kInfoMaxDeg, md);
-    raise_max(a.info + kInfoMaxN, mn);
-    raise_max(a.info + kInfoMaxE, me);
+    info_max(a.info + kInfoMaxDeg, md);
+    info_max(a.info + kInfoMaxN, mn);
+    info_max(a.info + kInfoMaxE, me);
   }
 }
 
@@ -565,7 +555,7 @@ __global__ void __launch_bounds__(256) unit_info_kernel(const int32_t *__restric
     ns = n1 - n0; es = (int)(e1 - e0);
   }
   ns = wave_max(ns); es = wave_max(es);
-  if (lane_id() == 0) { raise_max(info + kInfoChunkN, ns); raise_max(info + kInfoChunkE, es); }
+  if (lane_id() == 0) { info_max(info + kInfoChunkN, ns); info_max(info + kInfoChunkE, es); }
 }
 
 __global__ void __launch_bounds__(256) csr_ws_init_kernel(int64_t *__restrict__ states, int64_t nstates, int *__restrict__ ticket, int32_t *__restrict__ info) {
@@ -708,10 +698,10 @@ __global__ void __launch_bounds__(256) coo_ptr_kernel(const CooArgs a) {
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) allbad |= __shfl_xor(allbad, o);
   if (lane == 0) {
-    raise_max(a.info + kInfoMaxN, wmn);
-    raise_max(a.info + kInfoMaxE, wme);
-    raise_max(a.info + kInfoCooChunkN, wcn);
-    raise_max(a.info + kInfoCooChunkE, wce);
+    info_max(a.info + kInfoMaxN, wmn);
+    info_max(a.info + kInfoMaxE, wme);
+    info_max(a.info + kInfoCooChunkN, wcn);
+    info_max(a.info + kInfoCooChunkE, wce);
     if (anybad) atomicOr(a.info + kInfoStatus, allbad);
   }
 }
@@ -892,7 +882,7 @@ __global__ void __launch_bounds__(256) coo_fix_kernel(const CooArgs a) {
   }
   const int vs = (int)wave_sum64(viol), wmd = wave_max(md);
   if (lane == 0) {
-    raise_max(a.info + kInfoMaxDeg, wmd);
+    info_max(a.info + kInfoMaxDeg, wmd);
     if (any_sorted) atomicOr(a.info + kInfoSorted, 1);
     if (vs) atomicAdd(a.info + kInfoViol, vs);
     if (status) atomicOr(a.info + kInfoStatus, status);

@@ -21,11 +21,6 @@
 namespace {
 using namespace gtok;
 
-typedef const int32_t __attribute__((address_space(4))) *kptr32;
-typedef const int64_t __attribute__((address_space(4))) *kptr64;
-__device__ __forceinline__ int sload(const int32_t *p, int64_t i) { return ((kptr32)(uintptr_t)p)[i]; }
-__device__ __forceinline__ int64_t sload(const int64_t *p, int64_t i) { return ((kptr64)(uintptr_t)p)[i]; }
-
 struct RelabelArgs {
   gtok_csr g;
   const int32_t *tptr;        // the target's node_ptr
@@ -37,34 +32,6 @@ struct RelabelArgs {
   int stride, off_set, off_pre, nw;   // LDS bytes per wave, offsets of set / pre, words of set
   int units, upb;
 };
-
-__device__ __forceinline__ int wave_incl_scan(int v) {
-  const int lane = lane_id();
-#pragma unroll
-  for (int o = 1; o < kWave; o <<= 1) {
-    const int t = __shfl_up(v, o);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return uni(v);
-}
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = max(v, __shfl_xor(v, o));
-  return uni(v);
-}
-__device__ __forceinline__ int wave_min(int v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = min(v, __shfl_xor(v, o));
-  return uni(v);
-}
-__device__ __forceinline__ void info_max(int32_t *p, int v) {
-  if (v > __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p, v);
-}
 
 __global__ void __launch_bounds__(256) csr_relabel_kernel(const RelabelArgs a) {
   extern __shared__ __align__(16) unsigned char smem[];
@@ -111,7 +78,7 @@ __global__ void __launch_bounds__(256) csr_relabel_kernel(const RelabelArgs a) {
           ++named;
         }
       }
-      named = wave_sum(named);
+      named = uni(wave_sum(named));
       if (named != n) bad = 1;
       wave_sync();
       for (int i = lane; i < ((n + 31) >> 5); i += kWave) set[i] = 0;
@@ -197,7 +164,7 @@ __global__ void __launch_bounds__(256) csr_relabel_kernel(const RelabelArgs a) {
           lo = min(lo, cn >> 5); hi = max(hi, cn >> 5);
         }
         dup = __ballot(dup != 0) != 0 ? 1 : 0;
-        lo = wave_min(lo); hi = wave_max(hi);
+        lo = uni(wave_min(lo)); hi = uni(wave_max(hi));
         wave_sync();
         if (!dup) {
           int carry = 0;
@@ -239,7 +206,7 @@ __global__ void __launch_bounds__(256) csr_relabel_kernel(const RelabelArgs a) {
       atomicAdd(a.groups + 2 * (size_t)(r >> 6) + 1, (unsigned long long)e);
     }
     nonsimple += flag;
-    max_deg = max(max_deg, wave_max(dmax)); max_n = max(max_n, nt); max_e = max(max_e, e);
+    max_deg = max(max_deg, uni(wave_max(dmax))); max_n = max(max_n, nt); max_e = max(max_e, e);
   }
   if (lane == 0) {
     int32_t *info = a.out.info;
@@ -258,7 +225,7 @@ __global__ void __launch_bounds__(64) csr_relabel_chunks_kernel(const unsigned l
     cn = max(cn, (int)(x < 0x7FFFFFFFull ? x : 0x7FFFFFFFull));
     ce = max(ce, (int)(y < 0x7FFFFFFFull ? y : 0x7FFFFFFFull));
   }
-  cn = wave_max(cn); ce = wave_max(ce);
+  cn = uni(wave_max(cn)); ce = uni(wave_max(ce));
   if (lane == 0) { info[4] = cn; info[5] = ce; }
 }
 

@@ -12,7 +12,6 @@
 #include <cstdlib>
 
 #include "gtok_common.hpp"   // (and gtok.h)
-#include "gtok_sent_reg.hpp"   // sload(): scalar loads of the graph pointers
 
 namespace gtok {
 

@@ -11,16 +11,14 @@
 // row pointers scanned, the counters now row cursors - the scatter.  The scatter is STABLE: inside a step an entry's slot is
 // its row's cursor plus the number of earlier lanes of the step with the same row (found with one ballot per bit of the row
 // index), so a row lists its entries in list order (GraphBatch.from_coo).  Nothing is staged: the tokens are read again.
+// Everything around the parse and the scatter - the slice a row claims, the row-pointer scan, `info` - is
+// gtok_decode_csr.hpp's, shared with gtok_sent_decode.hip.
 #include "gtok_common.hpp"
-#include "gtok_ibtt_decode_args.hpp"
+#include "gtok_decode_args.hpp"
+#include "gtok_decode_csr.hpp"
 
 namespace {
 using namespace gtok;
-
-typedef const int32_t __attribute__((address_space(4))) *kptr32;
-typedef const int64_t __attribute__((address_space(4))) *kptr64;
-__device__ __forceinline__ int sload(const int32_t *p, int64_t i) { return ((kptr32)(uintptr_t)p)[i]; }
-__device__ __forceinline__ int64_t sload(const int64_t *p, int64_t i) { return ((kptr64)(uintptr_t)p)[i]; }
 
 enum { kZinc = GTOK_IBTT_GRAMMAR_ZINC, kSynth = GTOK_IBTT_GRAMMAR_SYNTH };
 
@@ -29,19 +27,6 @@ struct RowArgs {
   int eb, ld, rows, inv_len, maxn;
 };
 
-__device__ __forceinline__ int load_id(const RowArgs &a, int64_t at) {
-  if (a.eb == 1) return (int)static_cast<const uint8_t *>(a.ids)[at];
-  if (a.eb == 2) return (int)static_cast<const uint16_t *>(a.ids)[at];
-  return static_cast<const int32_t *>(a.ids)[at];
-}
-
-// first element and token count of row r; a negative start or an empty row: L = 0 (status 1)
-__device__ __forceinline__ void row_span(const RowArgs &a, int r, int64_t &base, int &L) {
-  base = a.row_start ? sload(a.row_start, r) : (int64_t)r * a.ld;
-  L = min(sload(a.len, r), a.ld);
-  if (base < 0 || L < 0) L = 0;
-}
-
 // class (LUT slot) of the row's token i; -1 for an id outside the vocab, an id no slot owns, or a position outside [0, L)
 __device__ __forceinline__ int cls_at(const RowArgs &a, int64_t base, int64_t i, int64_t L) {
   if (i < 0 || i >= L) return -1;
@@ -49,24 +34,6 @@ __device__ __forceinline__ int cls_at(const RowArgs &a, int64_t base, int64_t i,
   return (unsigned)id < (unsigned)a.inv_len ? a.inv[id] : -1;
 }
 __device__ __forceinline__ int ucls_at(const RowArgs &a, int64_t base, int64_t i, int64_t L) { return uni(cls_at(a, base, i, L)); }
-
-__device__ __forceinline__ int wave_incl_scan(int v) {
-  const int lane = lane_id();
-#pragma unroll
-  for (int o = 1; o < kWave; o <<= 1) {
-    const int t = __shfl_up(v, o);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = max(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ void info_max(int32_t *p, int v) {
-  if (v > __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p, v);
-}
 
 // lanes below the first set bit of `stop` (all of them when none is set)
 __device__ __forceinline__ uint64_t below_first(uint64_t stop) { return stop ? (1ull << __builtin_ctzll(stop)) - 1ull : ~0ull; }
@@ -294,52 +261,31 @@ __global__ void __launch_bounds__(256) ibtt_decode_csr_kernel(const CsrArgs a) {
   const int lane = lane_id();
   const int wave = wave_id(), wpb = (int)(blockDim.x >> 6);
   int *deg = reinterpret_cast<int *>(smem + (size_t)wave * a.stride);
-  const int rows = a.r.rows;
-  const int ntot = sload(a.out.node_ptr, rows);
-  const int64_t etot = sload(a.out.edge_ptr, rows);
-  int bad = 0, malformed = 0, unsorted = 0, max_deg = 0, max_n = 0, max_e = 0, chunk_n = 0, chunk_e = 0;
+  const DecodeTotals tot(a.out, a.r.rows);
+  DecodeInfo acc;                                  // info[0..7]: gtok_decode_csr.hpp
   const int vb = virtual_block();
   const int u0 = vb * a.upb, u1 = min(a.units, u0 + a.upb);
   for (int unit = u0; unit < u1; ++unit) {
     const int r = unit * wpb + wave;
-    if (r >= rows) break;
-    const int nb = sload(a.out.node_ptr, r), ne = sload(a.out.node_ptr, r + 1);
-    const int64_t e0 = sload(a.out.edge_ptr, r), e1 = sload(a.out.edge_ptr, r + 1);
-    if ((r & 63) == 0) {                           // the claimed sums of this aligned group of 64 graphs
-      const int rl = min(r + 64, rows);
-      const int64_t cn = (int64_t)sload(a.out.node_ptr, rl) - nb, ce = sload(a.out.edge_ptr, rl) - e0;
-      chunk_n = max(chunk_n, (int)min(max(cn, (int64_t)0), (int64_t)0x7FFFFFFF));
-      chunk_e = max(chunk_e, (int)min(max(ce, (int64_t)0), (int64_t)0x7FFFFFFF));
-    }
-    // a slice that lies inside the arrays the two pointer arrays describe; anything else is a row to skip
-    const bool slice_ok = nb >= 0 && ne >= nb && ne <= ntot && ne - nb <= a.r.maxn && e0 >= 0 && e1 >= e0 && e1 <= etot && e1 - e0 <= 0x7FFFFFFF;
+    if (r >= tot.rows) break;
+    const DecodeSlice sl = claim_slice(a.out, tot, r, a.r.maxn, acc);
+    const int nb = sl.nb;
+    const int64_t e0 = sl.e0;
     int64_t base; int L;
     row_span(a.r, r, base, L);
     const Shape s = row_shape<GR>(a.r, base, L);
     const int n = s.n, e = s.e;
-    if (s.st == 1) ++malformed;
-    if (!slice_ok || n != ne - nb || (int64_t)e != e1 - e0) { ++bad; continue; }
-    max_n = max(max_n, n); max_e = max(max_e, e);
+    if (s.st == 1) ++acc.malformed;
+    if (!sl.ok || n != sl.ncl || e != sl.ecl) { ++acc.bad; continue; }
+    acc.built(n, e);
     for (int u = lane; u < n; u += kWave) deg[u] = 0;            // (n <= maxn: inside this wave's counters)
     wave_sync();
     DegreeStep ds;
     ds.deg = deg; ds.n = n;
     for_entries<GR>(a.r, base, s, ds);
     wave_sync();
-    unsorted |= ds.unsorted;
-    // row pointers: the exclusive scan of the degrees; the counters become the rows' cursors
-    int32_t *rowptr = a.out.rowptr + nb + r;
-    int carry = 0, dmax = 0;
-    for (int u0n = 0; u0n < n; u0n += kWave) {
-      const int u = u0n + lane;
-      const int d = u < n ? deg[u] : 0;
-      const int incl = wave_incl_scan(d);
-      if (u < n) { rowptr[u] = carry + incl - d; deg[u] = carry + incl - d; }
-      dmax = max(dmax, d);
-      carry += __builtin_amdgcn_readlane(incl, kWave - 1);
-    }
-    if (lane == 0) rowptr[n] = e;
-    max_deg = max(max_deg, wave_max(dmax));
+    acc.unsorted |= ds.unsorted;
+    acc.max_deg = max(acc.max_deg, scan_rowptr(a.out.rowptr + nb + r, deg, n, e));   // the counters become the rows' cursors
     if (n == 0) continue;
     wave_sync();
     if (GR == kZinc)                                             // atom k's symbol is token 2 + 2 k
@@ -352,14 +298,7 @@ __global__ void __launch_bounds__(256) ibtt_decode_csr_kernel(const CsrArgs a) {
     ss.cursor = deg; ss.n = n; ss.e = e; ss.bits = n > 1 ? 32 - __builtin_clz(n - 1) : 0;
     for_entries<GR>(a.r, base, s, ss);
   }
-  if (lane == 0) {
-    int32_t *info = a.out.info;
-    if (bad) atomicAdd(info + 0, bad);
-    info_max(info + 1, max_deg); info_max(info + 2, max_n); info_max(info + 3, max_e);
-    info_max(info + 4, chunk_n); info_max(info + 5, chunk_e);
-    if (malformed) atomicAdd(info + 6, malformed);
-    info_max(info + 7, unsorted);
-  }
+  acc.report(a.out.info);
 }
 
 RowArgs row_args(const void *ids, int32_t elem_bytes, const int64_t *row_start, int32_t ld, const int32_t *len, int32_t num_rows,
@@ -375,31 +314,26 @@ RowArgs row_args(const void *ids, int32_t elem_bytes, const int64_t *row_start, 
 extern "C" int gtok_ibtt_decode_sizes(const void *ids, int32_t elem_bytes, const int64_t *row_start, int32_t ld, const int32_t *len,
                                       int32_t num_rows, int32_t grammar, const int32_t *inv, int32_t inv_len, int32_t max_num_nodes,
                                       int32_t *num_nodes, int32_t *num_entries, int32_t *status, int32_t *query, void *stream) {
-  const int c = gtok::ibtt_decode_check_rows(ids, elem_bytes, ld, len, num_rows, grammar, inv, inv_len, max_num_nodes);
-  if (c) return c < 0 ? c : GTOK_OK;
-  if (!num_nodes || !num_entries || !status) return GTOK_E_INVAL;
-  gtok::DeviceScope device_scope((hipStream_t)stream);   // the stream's device, not the thread's current one
-  if (!device_scope.ok()) return GTOK_E_NO_DEVICE;
-  SizesArgs a;
-  a.r = row_args(ids, elem_bytes, row_start, ld, len, num_rows, inv, inv_len, max_num_nodes);
-  a.num_nodes = num_nodes; a.num_entries = num_entries; a.status = status; a.query = query;
-  return grammar == kZinc ? launch_wave_per_item(ibtt_decode_sizes_kernel<kZinc>, a, num_rows, 4, 0, device_scope.dev, (hipStream_t)stream)
-                          : launch_wave_per_item(ibtt_decode_sizes_kernel<kSynth>, a, num_rows, 4, 0, device_scope.dev, (hipStream_t)stream);
+  const int c = ibtt_decode_check_rows(ids, elem_bytes, ld, len, num_rows, grammar, inv, inv_len, max_num_nodes);
+  return decode_launch(c, num_nodes && num_entries && status, nullptr, stream, [&](int dev, hipStream_t s) {
+    SizesArgs a;
+    a.r = row_args(ids, elem_bytes, row_start, ld, len, num_rows, inv, inv_len, max_num_nodes);
+    a.num_nodes = num_nodes; a.num_entries = num_entries; a.status = status; a.query = query;
+    return grammar == kZinc ? launch_wave_per_item(ibtt_decode_sizes_kernel<kZinc>, a, num_rows, 4, 0, dev, s)
+                            : launch_wave_per_item(ibtt_decode_sizes_kernel<kSynth>, a, num_rows, 4, 0, dev, s);
+  });
 }
 
 extern "C" int gtok_ibtt_decode_csr(const void *ids, int32_t elem_bytes, const int64_t *row_start, int32_t ld, const int32_t *len,
                                     int32_t num_rows, int32_t grammar, const int32_t *inv, int32_t inv_len, int32_t max_num_nodes,
                                     const gtok_csr_built *out, void *stream) {
-  const int c = gtok::ibtt_decode_check_rows(ids, elem_bytes, ld, len, num_rows, grammar, inv, inv_len, max_num_nodes);
-  if (c) return c < 0 ? c : GTOK_OK;
-  if (gtok::ibtt_decode_check_out(out, grammar) != GTOK_OK) return GTOK_E_INVAL;
-  gtok::DeviceScope device_scope((hipStream_t)stream);
-  if (!device_scope.ok()) return GTOK_E_NO_DEVICE;
-  if (hipMemsetAsync(out->info, 0, 8 * sizeof(int32_t), (hipStream_t)stream) != hipSuccess) return GTOK_E_LAUNCH;
-  CsrArgs a;
-  a.r = row_args(ids, elem_bytes, row_start, ld, len, num_rows, inv, inv_len, max_num_nodes);
-  a.out = *out;
-  a.stride = align_up((max_num_nodes > 0 ? max_num_nodes : 1) * 4, 16);
-  return grammar == kZinc ? launch_wave_per_item(ibtt_decode_csr_kernel<kZinc>, a, num_rows, 4, a.stride, device_scope.dev, (hipStream_t)stream)
-                          : launch_wave_per_item(ibtt_decode_csr_kernel<kSynth>, a, num_rows, 4, a.stride, device_scope.dev, (hipStream_t)stream);
+  const int c = ibtt_decode_check_rows(ids, elem_bytes, ld, len, num_rows, grammar, inv, inv_len, max_num_nodes);
+  return decode_launch(c, ibtt_decode_check_out(out, grammar) == GTOK_OK, out, stream, [&](int dev, hipStream_t s) {
+    CsrArgs a;
+    a.r = row_args(ids, elem_bytes, row_start, ld, len, num_rows, inv, inv_len, max_num_nodes);
+    a.out = *out;
+    a.stride = align_up((max_num_nodes > 0 ? max_num_nodes : 1) * 4, 16);
+    return grammar == kZinc ? launch_wave_per_item(ibtt_decode_csr_kernel<kZinc>, a, num_rows, 4, a.stride, dev, s)
+                            : launch_wave_per_item(ibtt_decode_csr_kernel<kSynth>, a, num_rows, 4, a.stride, dev, s);
+  });
 }

@@ -11,35 +11,19 @@
 // row's node_ptr / edge_ptr slice, staging the entries in LDS while they fit (up to 2,048); then - row pointers scanned,
 // the counters now row cursors - it scatters the entries, from the stage or, for a longer row, from a second parse.  The
 // scatter is STABLE: inside a batch an entry's slot is its row's cursor plus the number of earlier lanes of the batch with
-// the same row, so a row lists its entries in stream order (GraphBatch.from_coo).
+// the same row, so a row lists its entries in stream order (GraphBatch.from_coo).  Everything around the parse and the
+// scatter - the slice a row claims, the row-pointer scan, `info` - is gtok_decode_csr.hpp's, shared with gtok_ibtt_decode.hip.
 #include "gtok_common.hpp"
-#include "gtok_sent_decode_args.hpp"
+#include "gtok_decode_args.hpp"
+#include "gtok_decode_csr.hpp"
 
 namespace {
 using namespace gtok;
-
-typedef const int32_t __attribute__((address_space(4))) *kptr32;
-typedef const int64_t __attribute__((address_space(4))) *kptr64;
-__device__ __forceinline__ int sload(const int32_t *p, int64_t i) { return ((kptr32)(uintptr_t)p)[i]; }
-__device__ __forceinline__ int64_t sload(const int64_t *p, int64_t i) { return ((kptr64)(uintptr_t)p)[i]; }
 
 struct RowArgs {
   const void *ids; const int64_t *row_start; const int32_t *len;
   int eb, ld, rows, idx_off, node_off, edge_off, maxn;
 };
-
-__device__ __forceinline__ int load_id(const RowArgs &a, int64_t at) {
-  if (a.eb == 1) return (int)static_cast<const uint8_t *>(a.ids)[at];
-  if (a.eb == 2) return (int)static_cast<const uint16_t *>(a.ids)[at];
-  return static_cast<const int32_t *>(a.ids)[at];      // (as sent_decode_kernel reads them: a negative id is malformed wherever it stands)
-}
-
-// first element and token count of row r; a negative start or an empty row: L = 0 (status 1)
-__device__ __forceinline__ void row_span(const RowArgs &a, int r, int64_t &base, int &L) {
-  base = a.row_start ? sload(a.row_start, r) : (int64_t)r * a.ld;
-  L = min(sload(a.len, r), a.ld);
-  if (base < 0 || L < 0) L = 0;
-}
 
 // v with the wave-uniform value s in lane `at` (v_writelane's effect)
 __device__ __forceinline__ int put_lane(int s, int at, int v) { return lane_id() == at ? s : v; }
@@ -250,25 +234,6 @@ struct CsrArgs {
   int units, upb;
 };
 
-__device__ __forceinline__ int wave_incl_scan(int v) {
-  const int lane = lane_id();
-#pragma unroll
-  for (int o = 1; o < kWave; o <<= 1) {
-    const int t = __shfl_up(v, o);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = max(v, __shfl_xor(v, o));
-  return v;
-}
-// info[i] = max(info[i], v) / += v from one lane, skipped when it would change nothing
-__device__ __forceinline__ void info_max(int32_t *p, int v) {
-  if (v > __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p, v);
-}
-
 template <bool LAB>
 __global__ void __launch_bounds__(256) sent_decode_csr_kernel(const CsrArgs a) {
   extern __shared__ __align__(16) unsigned char smem[];
@@ -279,26 +244,16 @@ __global__ void __launch_bounds__(256) sent_decode_csr_kernel(const CsrArgs a) {
   int *stage_pk = reinterpret_cast<int *>(mine + a.deg_bytes);
   uint8_t *stage_t = reinterpret_cast<uint8_t *>(stage_pk + a.cap), *stage_nt = stage_t + a.cap;
   const int ncap = LAB && a.cap ? a.r.maxn : 0;
-  const int rows = a.r.rows;
-  const int ntot = sload(a.out.node_ptr, rows);
-  const int64_t etot = sload(a.out.edge_ptr, rows);
-  int bad = 0, malformed = 0, unsorted = 0, max_deg = 0, max_n = 0, max_e = 0, chunk_n = 0, chunk_e = 0;
+  const DecodeTotals tot(a.out, a.r.rows);
+  DecodeInfo acc;                                  // info[0..7]: gtok_decode_csr.hpp
   const int vb = virtual_block();
   const int u0 = vb * a.upb, u1 = min(a.units, u0 + a.upb);
   for (int unit = u0; unit < u1; ++unit) {
     const int r = unit * wpb + wave;
-    if (r >= rows) break;
-    const int nb = sload(a.out.node_ptr, r), ne = sload(a.out.node_ptr, r + 1);
-    const int64_t e0 = sload(a.out.edge_ptr, r), e1 = sload(a.out.edge_ptr, r + 1);
-    if ((r & 63) == 0) {                           // the claimed sums of this aligned group of 64 graphs
-      const int rl = min(r + 64, rows);
-      const int64_t cn = (int64_t)sload(a.out.node_ptr, rl) - nb, ce = sload(a.out.edge_ptr, rl) - e0;
-      chunk_n = max(chunk_n, (int)min(max(cn, (int64_t)0), (int64_t)0x7FFFFFFF));
-      chunk_e = max(chunk_e, (int)min(max(ce, (int64_t)0), (int64_t)0x7FFFFFFF));
-    }
-    // a slice that lies inside the arrays the two pointer arrays describe; anything else is a row to skip
-    const bool slice_ok = nb >= 0 && ne >= nb && ne <= ntot && ne - nb <= a.r.maxn && e0 >= 0 && e1 >= e0 && e1 <= etot && e1 - e0 <= 0x7FFFFFFF;
-    const int ncl = slice_ok ? ne - nb : 0, ecl = slice_ok ? (int)(e1 - e0) : 0;
+    if (r >= tot.rows) break;
+    const DecodeSlice sl = claim_slice(a.out, tot, r, a.r.maxn, acc);
+    const int nb = sl.nb, ncl = sl.ncl;
+    const int64_t e0 = sl.e0;
     for (int u = lane; u < ncl; u += kWave) deg[u] = 0;
     wave_sync();
     int64_t base; int L, n;
@@ -311,23 +266,11 @@ __global__ void __launch_bounds__(256) sent_decode_csr_kernel(const CsrArgs a) {
     if (LAB) ds.flush_nodes();
     wave_sync();
     int e = ds.entries;
-    if (st == 1) { n = 0; e = 0; ++malformed; }
-    if (!slice_ok || n != ncl || e != ecl) { ++bad; continue; }
-    unsorted |= st == 1 ? 0 : ds.unsorted;
-    max_n = max(max_n, n); max_e = max(max_e, e);
-    // row pointers: the exclusive scan of the degrees; the counters become the rows' cursors
-    int32_t *rowptr = a.out.rowptr + nb + r;
-    int carry = 0, dmax = 0;
-    for (int u0n = 0; u0n < n; u0n += kWave) {
-      const int u = u0n + lane;
-      const int d = u < n ? deg[u] : 0;
-      const int incl = wave_incl_scan(d);
-      if (u < n) { rowptr[u] = carry + incl - d; deg[u] = carry + incl - d; }
-      dmax = max(dmax, d);
-      carry += __builtin_amdgcn_readlane(incl, kWave - 1);
-    }
-    if (lane == 0) rowptr[n] = e;
-    max_deg = max(max_deg, wave_max(dmax));
+    if (st == 1) { n = 0; e = 0; ++acc.malformed; }
+    if (!sl.ok || n != ncl || e != sl.ecl) { ++acc.bad; continue; }
+    acc.unsorted |= st == 1 ? 0 : ds.unsorted;
+    acc.built(n, e);
+    acc.max_deg = max(acc.max_deg, scan_rowptr(a.out.rowptr + nb + r, deg, n, e));   // the counters become the rows' cursors
     if (st == 1 || n == 0) continue;
     wave_sync();
     ScatterSink<LAB> ss;
@@ -349,14 +292,7 @@ __global__ void __launch_bounds__(256) sent_decode_csr_kernel(const CsrArgs a) {
       if (LAB) ss.flush_nodes();
     }
   }
-  if (lane == 0) {
-    int32_t *info = a.out.info;
-    if (bad) atomicAdd(info + 0, bad);
-    info_max(info + 1, max_deg); info_max(info + 2, max_n); info_max(info + 3, max_e);
-    info_max(info + 4, chunk_n); info_max(info + 5, chunk_e);
-    if (malformed) atomicAdd(info + 6, malformed);
-    info_max(info + 7, unsorted);
-  }
+  acc.report(a.out.info);
 }
 
 RowArgs row_args(const void *ids, int32_t elem_bytes, const int64_t *row_start, int32_t ld, const int32_t *len, int32_t num_rows,
@@ -372,38 +308,33 @@ RowArgs row_args(const void *ids, int32_t elem_bytes, const int64_t *row_start, 
 extern "C" int gtok_sent_decode_sizes(const void *ids, int32_t elem_bytes, const int64_t *row_start, int32_t ld, const int32_t *len,
                                       int32_t num_rows, int32_t max_num_nodes, int32_t labeled, int32_t num_node_types,
                                       int32_t *num_nodes, int32_t *num_entries, int32_t *status, void *stream) {
-  const int c = gtok::sent_decode_check_rows(ids, elem_bytes, ld, len, num_rows, max_num_nodes, num_node_types);
-  if (c) return c < 0 ? c : GTOK_OK;
-  if (!num_nodes || !num_entries || !status) return GTOK_E_INVAL;
-  gtok::DeviceScope device_scope((hipStream_t)stream);   // the stream's device, not the thread's current one
-  if (!device_scope.ok()) return GTOK_E_NO_DEVICE;
-  SizesArgs a;
-  a.r = row_args(ids, elem_bytes, row_start, ld, len, num_rows, max_num_nodes, num_node_types);
-  a.num_nodes = num_nodes; a.num_entries = num_entries; a.status = status;
-  return labeled ? launch_wave_per_item(sent_decode_sizes_kernel<true>, a, num_rows, 4, 0, device_scope.dev, (hipStream_t)stream)
-                 : launch_wave_per_item(sent_decode_sizes_kernel<false>, a, num_rows, 4, 0, device_scope.dev, (hipStream_t)stream);
+  const int c = sent_decode_check_rows(ids, elem_bytes, ld, len, num_rows, max_num_nodes, num_node_types);
+  return decode_launch(c, num_nodes && num_entries && status, nullptr, stream, [&](int dev, hipStream_t s) {
+    SizesArgs a;
+    a.r = row_args(ids, elem_bytes, row_start, ld, len, num_rows, max_num_nodes, num_node_types);
+    a.num_nodes = num_nodes; a.num_entries = num_entries; a.status = status;
+    return labeled ? launch_wave_per_item(sent_decode_sizes_kernel<true>, a, num_rows, 4, 0, dev, s)
+                   : launch_wave_per_item(sent_decode_sizes_kernel<false>, a, num_rows, 4, 0, dev, s);
+  });
 }
 
 extern "C" int gtok_sent_decode_csr(const void *ids, int32_t elem_bytes, const int64_t *row_start, int32_t ld, const int32_t *len,
                                     int32_t num_rows, int32_t max_num_nodes, int32_t labeled, int32_t num_node_types,
                                     const gtok_csr_built *out, void *stream) {
-  const int c = gtok::sent_decode_check_rows(ids, elem_bytes, ld, len, num_rows, max_num_nodes, num_node_types);
-  if (c) return c < 0 ? c : GTOK_OK;
-  if (gtok::sent_decode_check_out(out, labeled) != GTOK_OK) return GTOK_E_INVAL;
-  gtok::DeviceScope device_scope((hipStream_t)stream);
-  if (!device_scope.ok()) return GTOK_E_NO_DEVICE;
-  if (hipMemsetAsync(out->info, 0, 8 * sizeof(int32_t), (hipStream_t)stream) != hipSuccess) return GTOK_E_LAUNCH;
-  CsrArgs a;
-  a.r = row_args(ids, elem_bytes, row_start, ld, len, num_rows, max_num_nodes, num_node_types);
-  a.out = *out;
-  a.deg_bytes = align_up((max_num_nodes > 0 ? max_num_nodes : 1) * 4, 16);
-  // the stage: a row of L tokens decodes to fewer than 2 L entries; 2,048 of them at the most (10 KB), and none where counters
-  // and stage together would pass what a workgroup has without the opt-in - every row is then parsed a second time, as rows of
-  // more entries than the stage holds always are
-  a.cap = align_up(ld < 1024 ? 2 * ld : 2048, 64);
-  int stage_bytes = a.cap * 4 + (labeled ? a.cap + align_up(max_num_nodes, 16) : 0);
-  if (a.deg_bytes + stage_bytes > kLdsWithoutOptIn) { a.cap = 0; stage_bytes = 0; }
-  a.stride = a.deg_bytes + stage_bytes;
-  return labeled ? launch_wave_per_item(sent_decode_csr_kernel<true>, a, num_rows, 4, a.stride, device_scope.dev, (hipStream_t)stream)
-                 : launch_wave_per_item(sent_decode_csr_kernel<false>, a, num_rows, 4, a.stride, device_scope.dev, (hipStream_t)stream);
+  const int c = sent_decode_check_rows(ids, elem_bytes, ld, len, num_rows, max_num_nodes, num_node_types);
+  return decode_launch(c, sent_decode_check_out(out, labeled) == GTOK_OK, out, stream, [&](int dev, hipStream_t s) {
+    CsrArgs a;
+    a.r = row_args(ids, elem_bytes, row_start, ld, len, num_rows, max_num_nodes, num_node_types);
+    a.out = *out;
+    a.deg_bytes = align_up((max_num_nodes > 0 ? max_num_nodes : 1) * 4, 16);
+    // the stage: a row of L tokens decodes to fewer than 2 L entries; 2,048 of them at the most (10 KB), and none where counters
+    // and stage together would pass what a workgroup has without the opt-in - every row is then parsed a second time, as rows of
+    // more entries than the stage holds always are
+    a.cap = align_up(ld < 1024 ? 2 * ld : 2048, 64);
+    int stage_bytes = a.cap * 4 + (labeled ? a.cap + align_up(max_num_nodes, 16) : 0);
+    if (a.deg_bytes + stage_bytes > kLdsWithoutOptIn) { a.cap = 0; stage_bytes = 0; }
+    a.stride = a.deg_bytes + stage_bytes;
+    return labeled ? launch_wave_per_item(sent_decode_csr_kernel<true>, a, num_rows, 4, a.stride, dev, s)
+                   : launch_wave_per_item(sent_decode_csr_kernel<false>, a, num_rows, 4, a.stride, dev, s);
+  });
 }

@@ -54,30 +54,6 @@ __device__ __forceinline__ void astore(int *p, int v) { __hip_atomic_store(p, v,
 __device__ __forceinline__ int aadd(int *p, int v) { return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void amin(unsigned *p, unsigned v) { (void)__hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-__device__ __forceinline__ int wave_incl_scan(int x) {
-  const int lane = lane_id();
-#pragma unroll
-  for (int o = 1; o < kWave; o <<= 1) {
-    const int y = __shfl_up(x, o);
-    x += lane >= o ? y : 0;
-  }
-  return x;
-}
-__device__ __forceinline__ int wave_sum(int x) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o);
-  return uni(x);
-}
-__device__ __forceinline__ int wave_min(int x) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) x = min(x, __shfl_xor(x, o));
-  return uni(x);
-}
-__device__ __forceinline__ int wave_max(int x) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) x = max(x, __shfl_xor(x, o));
-  return uni(x);
-}
 __device__ __forceinline__ unsigned wave_umin(unsigned x) {
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) x = min(x, (unsigned)__shfl_xor((int)x, o));
@@ -293,7 +269,7 @@ __global__ void __launch_bounds__(64) sent_large_kernel(const LargeArgs a) {
         klo = min(klo, kw); khi = max(khi, kw);
         if (TY) amin(reinterpret_cast<unsigned *>(key + kw), ((unsigned)dir << 31) | (unsigned)p);
       });
-      cntv = wave_sum(cntv); dead = wave_sum(dead); klo = wave_min(klo); khi = wave_max(khi);
+      cntv = uni(wave_sum(cntv)); dead = uni(wave_sum(dead)); klo = uni(wave_min(klo)); khi = uni(wave_max(khi));
       nlive -= dead;
       wave_sync();
       if (is0) {
@@ -369,13 +345,13 @@ __global__ void __launch_bounds__(64) sent_large_kernel(const LargeArgs a) {
               lo = min(lo, w); hi = max(hi, w);
             }
           });
-          lo = wave_min(lo); hi = wave_max(hi);
+          lo = uni(wave_min(lo)); hi = uni(wave_max(hi));
           wave_sync();
           if (hi >= 0) {
             const int wlo = lo >> 5, whi = (hi >> 5) + 1;
             int c = 0;
             for (int i = wlo + lane; i < whi; i += kWave) c += __popc(scr[i]);
-            c = wave_sum(c);
+            c = uni(wave_sum(c));
             const int nxt = select_kth([&](int i) { return scr[i]; }, wlo, whi, (int)below((uint32_t)c));
             for (int i = wlo + lane; i < whi; i += kWave) scr[i] = 0;
             wave_sync();

@@ -65,13 +65,6 @@ template <typename S> __device__ __forceinline__ int kth_bit_set(S word, int k) 
   return ctz_set((S)(eq & word));   // k < popcount(word): never empty
 }
 
-// Wave-uniform reads of the read-only graph pointers as SCALAR loads (constant address space): the
-// compiler will not prove invariance through the by-value argument struct on its own.
-typedef const int32_t __attribute__((address_space(4))) *kptr32;
-typedef const int64_t __attribute__((address_space(4))) *kptr64;
-__device__ __forceinline__ int sload(const int32_t *p, int64_t i) { return ((kptr32)(uintptr_t)p)[i]; }
-__device__ __forceinline__ int64_t sload(const int64_t *p, int64_t i) { return ((kptr64)(uintptr_t)p)[i]; }
-
 // remap_zinc_token restricted to node-type tokens (t = node_off + x >= node_off), branch-free:
 // train_agtt.py:209-230 — x < ntypes: atom 8+x if x < 9 else 22+t; otherwise the token sits in the edge
 // range: b = x - ntypes, bond 17+b if b < 4 else 22+t.

@@ -31,6 +31,12 @@ def _need_gpu(t: torch.Tensor, what: str) -> None:
         raise _lib.GtokError(f"{what}: tensors must live on the GPU (got {t.device}); the tokenizer has no CPU path")
 
 
+def _need(symbols, what: str) -> None:
+    """Entry points that came without an ABI version step (_lib.*_SYMBOLS): a library loaded through GTOK_LIB may lack them."""
+    if not all(hasattr(lib(), n) for n in symbols):
+        raise _lib.GtokError(f"{_lib.LIB_PATH} has no {what}: it was built before they were added")
+
+
 def _round4(v: int) -> int:
     return max(4, (int(v) + 3) // 4 * 4)
 
@@ -602,12 +608,6 @@ def sent_large(batch: GraphBatch, max_num_nodes: int, max_len: int, seed: int, e
     return ids.view(*shape, ld), ln.view(shape)
 
 
-def _need_order() -> None:
-    """gtok_sent_large_order / gtok_csr_relabel came without an ABI version step: a library loaded through GTOK_LIB may lack them."""
-    if not all(hasattr(lib(), n) for n in _lib.ORDER_SYMBOLS):
-        raise _lib.GtokError(f"{_lib.LIB_PATH} has no gtok_sent_large_order / gtok_csr_relabel: it was built before they were added")
-
-
 def sent_order(batch: GraphBatch, max_len: int, seed: int, epoch: int = 0, epochs: int = 1, graph_base: int = 0, with_rows: bool = False,
                max_num_nodes: Optional[int] = None, labeled: bool = False, num_node_types: int = 0, num_edge_types: int = 0,
                remap_zinc: bool = False, pad_id: int = SENT_PAD, query: Optional[torch.Tensor] = None, ld: Optional[int] = None,
@@ -620,7 +620,7 @@ def sent_order(batch: GraphBatch, max_len: int, seed: int, epoch: int = 0, epoch
     with_rows=True: -> (visit_index, ids, len), the rows ops.sent_large returns (its keywords), from the same launch.
     workspace: as ops.sent_large."""
     _need_gpu(batch.col, "sent_order")
-    _need_order()
+    _need(_lib.ORDER_SYMBOLS, "gtok_sent_large_order / gtok_csr_relabel")
     dev = batch.device
     K = max(1, int(epochs))
     G, N = batch.num_graphs, batch.num_nodes_total
@@ -851,10 +851,53 @@ def _decode_rows(ids: torch.Tensor, ln: torch.Tensor, row_start: Optional[torch.
     return ids.element_size(), ld, rows
 
 
-def _need_decode_csr() -> None:
-    """The two entry points came without an ABI version step: a library loaded through GTOK_LIB may lack them."""
-    if not all(hasattr(lib(), n) for n in _lib.DECODE_CSR_SYMBOLS):
-        raise _lib.GtokError(f"{_lib.LIB_PATH} has no gtok_sent_decode_sizes / gtok_sent_decode_csr: it was built before they were added")
+def _built_arrays(what: str, dev, G: int, N: int, E: int, nattr: bool, eattr: bool, node_ptr=None, edge_ptr=None, status: bool = False):
+    """Fresh arrays of a gtok_csr_built for G graphs of N nodes and E entries in all: -> (dict of the arrays, the C struct).  node_ptr /
+    edge_ptr: the caller's own where the call reads them (pass 2 of the decoders), checked here and part of the dict; nattr / eattr
+    None when not asked for; status: an int32 [G] beside them.  info is zero when G == 0 (the caller then launches nothing)."""
+    if node_ptr is not None and (
+            node_ptr.dtype != torch.int32 or edge_ptr.dtype != torch.int64 or node_ptr.numel() != G + 1 or edge_ptr.numel() != G + 1
+            or not node_ptr.is_contiguous() or not edge_ptr.is_contiguous() or node_ptr.device != dev or edge_ptr.device != dev):
+        raise ValueError(f"{what}: node_ptr int32 [rows + 1] and edge_ptr int64 [rows + 1] on the rows' device")
+    N, E = int(N), int(E)
+    if N < 0 or E < 0 or N + G >= 2 ** 31:
+        raise ValueError(f"{what}: totals out of range (a batch holds fewer than 2^31 nodes + graphs; shard it)")
+    # (the library wants an address for every array, and an empty tensor has none: one spare element, sliced off)
+    new = lambda n, dt: torch.empty(n + 1, dtype=dt, device=dev)
+    full = dict(rowptr=new(N + G, torch.int32), col=new(E, torch.int32), eorder=new(E, torch.int32),
+                nattr=new(N, torch.uint8) if nattr else None, eattr=new(E, torch.uint8) if eattr else None, info=new(8, torch.int32))
+    if status:
+        full["status"] = new(G, torch.int32)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    cout = _lib.GtokCsrBuilt(ptr(node_ptr), ptr(edge_ptr), *[ptr(full[n]) for n in ("rowptr", "col", "eorder", "nattr", "eattr", "info")])
+    o = {k: None if t is None else t[:-1] for k, t in full.items()}
+    if node_ptr is not None:
+        o = dict(node_ptr=node_ptr, edge_ptr=edge_ptr, **o)
+    if G == 0:
+        o["info"].zero_()
+    return o, cout
+
+
+def _decoded_batch(what: str, nn: torch.Tensor, ne: torch.Tensor, launch, check_symmetric: bool) -> GraphBatch:
+    """The second half of sent_decode_csr / ibtt_decode_csr: the sizes of pass 1 prefix-summed, their totals read back, pass 2 -
+    launch(node_ptr, edge_ptr, N, E) -> the dict of its arrays - and `info` read back into the GraphBatch's maxima."""
+    dev, rows = nn.device, int(nn.numel())
+    node_ptr64 = torch.zeros(rows + 1, dtype=torch.int64, device=dev); torch.cumsum(nn, 0, dtype=torch.int64, out=node_ptr64[1:])
+    edge_ptr = torch.zeros(rows + 1, dtype=torch.int64, device=dev); torch.cumsum(ne, 0, dtype=torch.int64, out=edge_ptr[1:])
+    N, E = torch.stack([node_ptr64[-1], edge_ptr[-1]]).tolist()            # the read-back of the two totals
+    if N + rows >= 2 ** 31:
+        raise ValueError("batch too large for int32 node offsets; shard it")
+    o = launch(node_ptr64.to(torch.int32), edge_ptr, N, E)
+    v = o["info"].tolist()                                                  # ... and of info
+    if v[0]:
+        raise _lib.GtokError(f"{what}: {v[0]} rows changed between the two passes")
+    b = GraphBatch(rows, v[2], v[3], o["node_ptr"], o["edge_ptr"], o["rowptr"], o["col"], o["eorder"] if v[7] else None, o["nattr"], o["eattr"],
+                   0, v[4], v[5], v[1] if N else 0)
+    if check_symmetric and E:
+        if csr_check(b)["violations"] == 0:
+            b.flags |= _lib.CSR_SIMPLE_SYMMETRIC
+        b.checked = True
+    return b
 
 
 def sent_decode_sizes(ids: torch.Tensor, ln: torch.Tensor, max_num_nodes: int, labeled: bool = False, num_node_types: int = 0,
@@ -862,7 +905,7 @@ def sent_decode_sizes(ids: torch.Tensor, ln: torch.Tensor, max_num_nodes: int, l
     """gtok_sent_decode_sizes: (num_nodes, num_entries, status) int32 [rows] of un-remapped SENT rows - the sizes of the graphs
     sent_decode_csr builds (a status-1 row: 0, 0).  ids / row_start / ld as there.  Nothing is read back."""
     eb, ld, rows = _decode_rows(ids, ln, row_start, ld, "sent_decode_sizes")
-    _need_decode_csr()
+    _need(_lib.DECODE_CSR_SYMBOLS, "gtok_sent_decode_sizes / gtok_sent_decode_csr")
     dev = ids.device
     nn, ne, st = (torch.empty(rows, dtype=torch.int32, device=dev) for _ in range(3))
     if rows:
@@ -876,24 +919,12 @@ def _decode_csr_launch(ids, ln, row_start, ld, max_num_nodes, labeled, num_node_
     """gtok_sent_decode_csr on the current stream into fresh arrays of the given totals: -> dict of gtok_csr_built's arrays
     (nattr / eattr None when unlabelled); no host read."""
     eb, ld, rows = _decode_rows(ids, ln, row_start, ld, "sent_decode_csr")
-    _need_decode_csr()
+    _need(_lib.DECODE_CSR_SYMBOLS, "gtok_sent_decode_sizes / gtok_sent_decode_csr")
     dev = ids.device
-    if node_ptr.dtype != torch.int32 or edge_ptr.dtype != torch.int64 or node_ptr.numel() != rows + 1 or edge_ptr.numel() != rows + 1 \
-            or not node_ptr.is_contiguous() or not edge_ptr.is_contiguous() or node_ptr.device != dev or edge_ptr.device != dev:
-        raise ValueError("sent_decode_csr: node_ptr int32 [rows + 1] and edge_ptr int64 [rows + 1] on the rows' device")
-    N, E = int(N), int(E)
-    if N < 0 or E < 0 or N + rows >= 2 ** 31:
-        raise ValueError("sent_decode_csr: totals out of range (a batch holds fewer than 2^31 nodes + graphs; shard it)")
-    # (the library wants an address for every array, and an empty tensor has none: one spare element, sliced off)
-    new = lambda n, dt: torch.empty(n + 1, dtype=dt, device=dev)
-    full = dict(node_ptr=node_ptr, edge_ptr=edge_ptr, rowptr=new(N + rows, torch.int32), col=new(E, torch.int32), eorder=new(E, torch.int32),
-                nattr=new(N, torch.uint8) if labeled else None, eattr=new(E, torch.uint8) if labeled else None, info=new(8, torch.int32))
-    o = {k: t if t is None or k in ("node_ptr", "edge_ptr") else t[:-1] for k, t in full.items()}
+    o, cout = _built_arrays("sent_decode_csr", dev, rows, N, E, labeled, labeled, node_ptr, edge_ptr)
     if rows == 0:
-        o["info"].zero_()
         return o
     ptr = lambda t: None if t is None else t.data_ptr()
-    cout = _lib.GtokCsrBuilt(*[ptr(full[n]) for n, _ in _lib.GtokCsrBuilt._fields_])
     check(lib().gtok_sent_decode_csr(ids.data_ptr(), eb, ptr(row_start), ld, ln.data_ptr(), rows, int(max_num_nodes), int(bool(labeled)),
                                      int(num_node_types), ctypes.byref(cout), _stream(dev)), "gtok_sent_decode_csr")
     return o
@@ -913,23 +944,8 @@ def sent_decode_csr(ids: torch.Tensor, ln: torch.Tensor, max_num_nodes: int, lab
     result sets CSR_SIMPLE_SYMMETRIC when every graph is simple (a third read-back); a batch without a single entry is left
     unflagged and unchecked, as GraphBatch.from_coo leaves it."""
     nn, ne, status = sent_decode_sizes(ids, ln, max_num_nodes, labeled, num_node_types, row_start, ld)
-    dev, rows = ids.device, int(ln.numel())
-    node_ptr64 = torch.zeros(rows + 1, dtype=torch.int64, device=dev); torch.cumsum(nn, 0, dtype=torch.int64, out=node_ptr64[1:])
-    edge_ptr = torch.zeros(rows + 1, dtype=torch.int64, device=dev); torch.cumsum(ne, 0, dtype=torch.int64, out=edge_ptr[1:])
-    N, E = torch.stack([node_ptr64[-1], edge_ptr[-1]]).tolist()            # the read-back of the two totals
-    if N + rows >= 2 ** 31:
-        raise ValueError("batch too large for int32 node offsets; shard it")
-    o = _decode_csr_launch(ids, ln, row_start, ld, max_num_nodes, labeled, num_node_types, node_ptr64.to(torch.int32), edge_ptr, N, E)
-    v = o["info"].tolist()                                                  # ... and of info
-    if v[0]:
-        raise _lib.GtokError(f"sent_decode_csr: {v[0]} rows changed between the two passes")
-    b = GraphBatch(rows, v[2], v[3], o["node_ptr"], o["edge_ptr"], o["rowptr"], o["col"], o["eorder"] if v[7] else None, o["nattr"], o["eattr"],
-                   0, v[4], v[5], v[1] if N else 0)
-    if check_symmetric and E:
-        if csr_check(b)["violations"] == 0:
-            b.flags |= _lib.CSR_SIMPLE_SYMMETRIC
-        b.checked = True
-    return b, status
+    launch = lambda node_ptr, edge_ptr, N, E: _decode_csr_launch(ids, ln, row_start, ld, max_num_nodes, labeled, num_node_types, node_ptr, edge_ptr, N, E)
+    return _decoded_batch("sent_decode_csr", nn, ne, launch, check_symmetric), status
 
 
 # ------------------------------------------------------------------------------------------------
@@ -966,11 +982,6 @@ def ibtt_inverse_lut(lut, vocab_size: int, pad_id: Optional[int] = None) -> torc
     return torch.from_numpy(inv)
 
 
-def _need_ibtt_decode() -> None:
-    if not all(hasattr(lib(), n) for n in _lib.IBTT_DECODE_SYMBOLS):
-        raise _lib.GtokError(f"{_lib.LIB_PATH} has no gtok_ibtt_decode_sizes / gtok_ibtt_decode_csr: it was built before they were added")
-
-
 def _ibtt_inv(inv: torch.Tensor, dev) -> torch.Tensor:
     if inv.dim() != 1 or inv.numel() < 1:
         raise ValueError("inv is a non-empty int32 vector (ibtt_inverse_lut)")
@@ -983,7 +994,7 @@ def ibtt_decode_sizes(ids: torch.Tensor, ln: torch.Tensor, grammar, inv: torch.T
     ibtt_decode_csr builds (a status-1 row: 0, 0) - and, with_query (graph-token rows), query int32 [rows, 4].  ids / row_start /
     ld as sent_decode_csr.  Nothing is read back."""
     eb, ld, rows = _decode_rows(ids, ln, row_start, ld, "ibtt_decode_sizes")
-    _need_ibtt_decode()
+    _need(_lib.IBTT_DECODE_SYMBOLS, "gtok_ibtt_decode_sizes / gtok_ibtt_decode_csr")
     g = _ibtt_grammar(grammar)
     dev = ids.device
     inv = _ibtt_inv(inv, dev)
@@ -1001,26 +1012,15 @@ def _ibtt_decode_csr_launch(ids, ln, row_start, ld, grammar, inv, max_num_nodes,
     """gtok_ibtt_decode_csr on the current stream into fresh arrays of the given totals: -> dict of gtok_csr_built's arrays
     (nattr / eattr None for graph-token rows); no host read."""
     eb, ld, rows = _decode_rows(ids, ln, row_start, ld, "ibtt_decode_csr")
-    _need_ibtt_decode()
+    _need(_lib.IBTT_DECODE_SYMBOLS, "gtok_ibtt_decode_sizes / gtok_ibtt_decode_csr")
     g = _ibtt_grammar(grammar)
     dev = ids.device
     inv = _ibtt_inv(inv, dev)
-    if node_ptr.dtype != torch.int32 or edge_ptr.dtype != torch.int64 or node_ptr.numel() != rows + 1 or edge_ptr.numel() != rows + 1 \
-            or not node_ptr.is_contiguous() or not edge_ptr.is_contiguous() or node_ptr.device != dev or edge_ptr.device != dev:
-        raise ValueError("ibtt_decode_csr: node_ptr int32 [rows + 1] and edge_ptr int64 [rows + 1] on the rows' device")
-    N, E = int(N), int(E)
-    if N < 0 or E < 0 or N + rows >= 2 ** 31:
-        raise ValueError("ibtt_decode_csr: totals out of range (a batch holds fewer than 2^31 nodes + graphs; shard it)")
     typed = g == _lib.IBTT_GRAMMAR_ZINC
-    new = lambda n, dt: torch.empty(n + 1, dtype=dt, device=dev)      # (one spare element: an empty tensor has no address)
-    full = dict(node_ptr=node_ptr, edge_ptr=edge_ptr, rowptr=new(N + rows, torch.int32), col=new(E, torch.int32), eorder=new(E, torch.int32),
-                nattr=new(N, torch.uint8) if typed else None, eattr=new(E, torch.uint8) if typed else None, info=new(8, torch.int32))
-    o = {k: t if t is None or k in ("node_ptr", "edge_ptr") else t[:-1] for k, t in full.items()}
+    o, cout = _built_arrays("ibtt_decode_csr", dev, rows, N, E, typed, typed, node_ptr, edge_ptr)
     if rows == 0:
-        o["info"].zero_()
         return o
     ptr = lambda t: None if t is None else t.data_ptr()
-    cout = _lib.GtokCsrBuilt(*[ptr(full[n]) for n, _ in _lib.GtokCsrBuilt._fields_])
     check(lib().gtok_ibtt_decode_csr(ids.data_ptr(), eb, ptr(row_start), ld, ln.data_ptr(), rows, g, inv.data_ptr(), inv.numel(),
                                      int(max_num_nodes), ctypes.byref(cout), _stream(dev)), "gtok_ibtt_decode_csr")
     return o
@@ -1038,22 +1038,8 @@ def ibtt_decode_csr(ids: torch.Tensor, ln: torch.Tensor, grammar, inv: torch.Ten
     synth = g == _lib.IBTT_GRAMMAR_SYNTH
     sizes = ibtt_decode_sizes(ids, ln, g, inv, max_num_nodes, row_start, ld, with_query=synth)
     nn, ne, status = sizes[:3]
-    dev, rows = ids.device, int(ln.numel())
-    node_ptr64 = torch.zeros(rows + 1, dtype=torch.int64, device=dev); torch.cumsum(nn, 0, dtype=torch.int64, out=node_ptr64[1:])
-    edge_ptr = torch.zeros(rows + 1, dtype=torch.int64, device=dev); torch.cumsum(ne, 0, dtype=torch.int64, out=edge_ptr[1:])
-    N, E = torch.stack([node_ptr64[-1], edge_ptr[-1]]).tolist()            # the read-back of the two totals
-    if N + rows >= 2 ** 31:
-        raise ValueError("batch too large for int32 node offsets; shard it")
-    o = _ibtt_decode_csr_launch(ids, ln, row_start, ld, g, inv, max_num_nodes, node_ptr64.to(torch.int32), edge_ptr, N, E)
-    v = o["info"].tolist()                                                  # ... and of info
-    if v[0]:
-        raise _lib.GtokError(f"ibtt_decode_csr: {v[0]} rows changed between the two passes")
-    b = GraphBatch(rows, v[2], v[3], o["node_ptr"], o["edge_ptr"], o["rowptr"], o["col"], o["eorder"] if v[7] else None, o["nattr"], o["eattr"],
-                   0, v[4], v[5], v[1] if N else 0)
-    if check_symmetric and E:
-        if csr_check(b)["violations"] == 0:
-            b.flags |= _lib.CSR_SIMPLE_SYMMETRIC
-        b.checked = True
+    launch = lambda node_ptr, edge_ptr, N, E: _ibtt_decode_csr_launch(ids, ln, row_start, ld, g, inv, max_num_nodes, node_ptr, edge_ptr, N, E)
+    b = _decoded_batch("ibtt_decode_csr", nn, ne, launch, check_symmetric)
     return (b, status, sizes[3]) if synth else (b, status)
 
 
@@ -1066,7 +1052,7 @@ _RELABEL_WS = {}
 def _relabel_launch(batch: GraphBatch, old_of_new: torch.Tensor, target_node_ptr: torch.Tensor, target_max_nodes: int, total: int) -> dict:
     """gtok_csr_relabel on the current stream into fresh arrays: -> dict(rowptr, col, eorder, nattr, eattr, info, status); no host read."""
     _need_gpu(batch.col, "csr_relabel")
-    _need_order()
+    _need(_lib.ORDER_SYMBOLS, "gtok_sent_large_order / gtok_csr_relabel")
     dev, G, E = batch.device, batch.num_graphs, batch.num_edges_total
     total = int(total)
     if old_of_new.dtype != torch.int32 or old_of_new.dim() != 1 or not old_of_new.is_contiguous() or old_of_new.device != dev \
@@ -1074,16 +1060,8 @@ def _relabel_launch(batch: GraphBatch, old_of_new: torch.Tensor, target_node_ptr
         raise ValueError("csr_relabel: old_of_new must be a contiguous int32 vector of one entry per target node on the batch's device")
     if target_node_ptr.dtype != torch.int32 or target_node_ptr.numel() != G + 1 or not target_node_ptr.is_contiguous() or target_node_ptr.device != dev:
         raise ValueError("csr_relabel: target_node_ptr must be a contiguous int32 [G + 1] on the batch's device")
-    if total < 0 or total + G >= 2 ** 31:
-        raise ValueError("csr_relabel: totals out of range (a batch holds fewer than 2^31 nodes + graphs; shard it)")
-    has_n, has_e = batch.nattr is not None, batch.eattr is not None
-    new = lambda n, dt: torch.empty(n + 1, dtype=dt, device=dev)       # (one spare element: an empty tensor has no address)
-    full = dict(rowptr=new(total + G, torch.int32), col=new(E, torch.int32), eorder=new(E, torch.int32),
-                nattr=new(total, torch.uint8) if has_n else None, eattr=new(E, torch.uint8) if has_e else None, info=new(8, torch.int32),
-                status=new(G, torch.int32))
-    o = {k: None if t is None else t[:-1] for k, t in full.items()}
+    o, cout = _built_arrays("csr_relabel", dev, G, total, E, batch.nattr is not None, batch.eattr is not None, status=True)
     if G == 0:
-        o["info"].zero_()
         return o
     need = int(lib().gtok_csr_relabel_workspace(G, E))
     if need < 0:
@@ -1092,13 +1070,10 @@ def _relabel_launch(batch: GraphBatch, old_of_new: torch.Tensor, target_node_ptr
     ws = _RELABEL_WS.get(key)
     if ws is None or ws.numel() < need:
         ws = _RELABEL_WS[key] = torch.empty(max(16, need), dtype=torch.uint8, device=dev)
-    ptr = lambda t: None if t is None else t.data_ptr()
-    cout = _lib.GtokCsrBuilt(None, None, ptr(full["rowptr"]), ptr(full["col"]), ptr(full["eorder"]), ptr(full["nattr"]), ptr(full["eattr"]),
-                             ptr(full["info"]))
     cs = batch.c_struct()
     oon = old_of_new if total else torch.empty(1, dtype=torch.int32, device=dev)
     check(lib().gtok_csr_relabel(ctypes.byref(cs), target_node_ptr.data_ptr(), int(target_max_nodes), oon.data_ptr(), ctypes.byref(cout),
-                                 full["status"].data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)), "gtok_csr_relabel")
+                                 o["status"].data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)), "gtok_csr_relabel")
     return o
 
 

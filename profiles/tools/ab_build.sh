@@ -7,9 +7,8 @@ root=$(git rev-parse --show-toplevel)
 tmp=$(mktemp -d)
 git -C "$root" archive "$ref" glearning-benchmark_amd/csrc include | tar -x -C "$tmp"
 mkdir -p "$root/glearning-benchmark_amd/csrc/_ab"
-for f in gtok_sent gtok_sent_large gtok_ibtt gtok_text gtok_rows gtok_csr; do   # (a ref from before a file existed: skipped)
-  [ -f "$tmp/glearning-benchmark_amd/csrc/$f.hip" ] || continue
-  /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -c -I"$tmp/include" -o "$tmp/$f.o" "$tmp/glearning-benchmark_amd/csrc/$f.hip" &
+for src in "$tmp"/glearning-benchmark_amd/csrc/*.hip; do   # every source file the ref has
+  /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -c -I"$tmp/include" -o "$tmp/$(basename "$src" .hip).o" "$src" &
 done
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -fPIC -shared -o "$root/glearning-benchmark_amd/csrc/_ab/libgtok_$name.so" "$tmp"/*.o

@@ -75,7 +75,8 @@ def bodies(directory):
 def demangle(names):
     try:
         text = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True, check=True).stdout.split("\n")
-        return dict(zip(names, (re.sub(r"^void |\(.*$", "", t).replace("gtok::", "") for t in text)))
+        # (a kernel of an unnamed namespace demangles to "(anonymous namespace)::name<..>(..)": that prefix goes before the cut at the argument list)
+        return dict(zip(names, (re.sub(r"^void |\(.*$", "", t.replace("(anonymous namespace)::", "")).replace("gtok::", "") for t in text)))
     except (OSError, subprocess.CalledProcessError):
         return {n: n for n in names}
 

@@ -1,12 +1,12 @@
 // Stand-alone program over the host-side argument checks of gtok_ibtt_decode_sizes / gtok_ibtt_decode_csr
-// (csrc/gtok_ibtt_decode_args.hpp), to be run under the host sanitizers on a machine without a GPU:
+// (csrc/gtok_decode_args.hpp), to be run under the host sanitizers on a machine without a GPU:
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude -Iglearning-benchmark_amd/csrc \
 //       tests/host/ibtt_decode_args_main.cpp -o /tmp/ibtt_decode_args && /tmp/ibtt_decode_args
 // Exit status 0 and "0 failures": every check answered as include/gtok.h documents and no sanitizer spoke.
 #include <cstdio>
 #include <vector>
 
-#include "gtok_ibtt_decode_args.hpp"
+#include "gtok_decode_args.hpp"
 
 static int failures = 0;
 #define EXPECT(expr, want)                                                        \
