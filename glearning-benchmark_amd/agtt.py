@@ -114,6 +114,13 @@ class TokenizedGraphDataset(Dataset):
         self._ids, self._lens = sl[0][e], sl[1][e]
         return self._ids, self._lens
 
+    def decode_rows(self, ids: torch.Tensor, ln: torch.Tensor, row_start: Optional[torch.Tensor] = None):
+        """Rows of this dataset (tokenize_epoch's / tokenize_epoch_u16's slabs, packed rows with row_start, or what a model trained on
+        them emits) -> (GraphBatch in visit-index space, status int32 [rows]) on the device: the tokenizer's decode_batch_zinc when the
+        dataset remaps to the fixed vocabulary, its decode_batch otherwise.  A query tail behind EOS is not parsed."""
+        decode = self.tokenizer.decode_batch_zinc if self.remap_to_fixed_vocab else self.tokenizer.decode_batch
+        return decode(ids, ln, row_start=row_start)
+
     def remap_zinc_tokens(self, tokens: torch.Tensor, data=None) -> torch.Tensor:
         """1-D raw SENT ids -> fixed-vocab ids through gtok_remap_zinc (same table as the fused path)."""
         t = tokens.to(self._dev(), dtype=torch.int32).view(1, -1).contiguous()

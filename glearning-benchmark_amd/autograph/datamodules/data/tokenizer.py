@@ -130,6 +130,10 @@ class Graph2TrailTokenizer:
         ops.graphs_equal then compares the result with the input - with its symmetric closure, where the input lists every edge
         once.  status is the decoder's; rows and an order of different walks (another seed, epoch, graph_base, max length) raise."""
         b, status = self.decode_batch(ids, ln, row_start=row_start)
+        return self._like(b, status, like, order, check_symmetric)
+
+    def _like(self, b: "GraphBatch", status: torch.Tensor, like: "GraphBatch", order: torch.Tensor, check_symmetric: bool):
+        """decode_batch_like / decode_batch_like_zinc behind their decoders: the decoded batch b in the numbering of `like`."""
         G, N = like.num_graphs, like.num_nodes_total
         K = b.num_graphs // G if G else 1
         if b.num_graphs != K * G or int(order.numel()) != K * N:
@@ -154,13 +158,16 @@ class Graph2TrailTokenizer:
         """One sequence (a 1-D tensor of un-remapped ids, as tokenizer(data) returns them) -> dict(num_nodes, edge_index int64 [2, E]
         with both directions of every edge in stream order, x int64 [num_nodes] and edge_attr int64 [E] (None when unlabelled; 255 =
         no type), status) on the host."""
+        return self._decode_one(tokens, self.decode_batch)
+
+    def _decode_one(self, tokens, decode_batch) -> dict:
         t = torch.as_tensor(tokens).reshape(1, -1).to(self._device(), dtype=torch.int32).contiguous()
         if t.shape[1] == 0:
             t = torch.full((1, 1), self.pad, dtype=torch.int32, device=t.device)
             ln = torch.zeros(1, dtype=torch.int32, device=t.device)
         else:
             ln = torch.full((1,), t.shape[1], dtype=torch.int32, device=t.device)
-        b, status = self.decode_batch(t, ln)
+        b, status = decode_batch(t, ln)
         n, e = int(b.node_ptr[1]), int(b.edge_ptr[1])
         counts = (b.rowptr[1:n + 1] - b.rowptr[:n]).to(torch.int64)
         src = torch.repeat_interleave(torch.arange(n, device=t.device), counts, output_size=e)
@@ -168,6 +175,31 @@ class Graph2TrailTokenizer:
         edge_index = torch.stack([src, b.col.to(torch.int64)])[:, order]
         long = lambda a, o=None: None if a is None else (a if o is None else a[o]).to(torch.int64).cpu()
         return dict(num_nodes=n, edge_index=edge_index.cpu(), x=long(b.nattr), edge_attr=long(b.eattr, order), status=int(status[0]))
+
+    # ---- ... from ZINC-remapped rows (tokenize_batch(remap_zinc=True): what every ZINC run trains on); labelled graphs only
+    def _need_labeled(self, what: str) -> None:
+        if not self.labeled_graph:
+            raise ValueError(f"{what}: only labelled rows are remapped - unlabelled remapped rows are ambiguous (labeled_graph=True)")
+        if self.max_num_nodes is None:
+            raise RuntimeError("call set_num_nodes() first")
+
+    def decode_batch_zinc(self, ids: torch.Tensor, ln: torch.Tensor, row_start: Optional[torch.Tensor] = None, check_symmetric: bool = False):
+        """decode_batch for ZINC-remapped rows (slabs, int32 or 16-bit, or packed rows - 8-bit ones included - with row_start):
+        ops.sent_decode_zinc_csr with this tokenizer's max_num_nodes and num_node_types.  The result is decode_batch's over the
+        un-remapped rows of the same walk."""
+        self._need_labeled("decode_batch_zinc")
+        return _ops.sent_decode_zinc_csr(ids, ln, self.max_num_nodes, self.num_node_types, row_start=row_start, check_symmetric=check_symmetric)
+
+    def decode_batch_like_zinc(self, ids: torch.Tensor, ln: torch.Tensor, like: "GraphBatch", order: torch.Tensor,
+                               row_start: Optional[torch.Tensor] = None, check_symmetric: bool = False):
+        """decode_batch_like for ZINC-remapped rows: order = visit_order's result for the same walk (the remap does not change it)."""
+        b, status = self.decode_batch_zinc(ids, ln, row_start=row_start)
+        return self._like(b, status, like, order, check_symmetric)
+
+    def decode_zinc(self, tokens) -> dict:
+        """decode for one sequence of ZINC-remapped ids (a dataset item of a remapping TokenizedGraphDataset)."""
+        self._need_labeled("decode_zinc")
+        return self._decode_one(tokens, self.decode_batch_zinc)
 
     EPOCH_WALKS = 1 << 22         # walks per launch: sixteen rounds of the 4,096 resident waves x 64 lanes of sent_lane_kernel - units that
                                   # are staged and padded while other waves walk cost less than those of a one-round launch, and the

@@ -1,5 +1,5 @@
 // gtok_decode_args.hpp - the host-side argument checks of the row decoders (gtok_sent_decode_sizes / gtok_sent_decode_csr,
-// gtok_ibtt_decode_sizes / gtok_ibtt_decode_csr), in a header of their own (no HIP in it) so that a plain C++ program can
+// gtok_ibtt_decode_sizes / gtok_ibtt_decode_csr, gtok_unremap_zinc and the gtok_sent_decode_zinc_* pair), in a header of their own (no HIP in it) so that a plain C++ program can
 // exercise them under the host sanitizers.
 #pragma once
 #include <stdint.h>
@@ -41,5 +41,15 @@ inline int ibtt_decode_check_rows(const void *ids, int32_t elem_bytes, int32_t l
 // labelled SENT rows and molecule IBTT rows carry types
 inline int sent_decode_check_out(const gtok_csr_built *out, int32_t labeled) { return decode_check_out(out, labeled != 0); }
 inline int ibtt_decode_check_out(const gtok_csr_built *out, int32_t grammar) { return decode_check_out(out, grammar == GTOK_IBTT_GRAMMAR_ZINC); }
+
+// ZINC-remapped SENT rows (gtok_unremap_zinc, gtok_sent_decode_zinc_sizes / gtok_sent_decode_zinc_csr): the rows are checked as the
+// un-remapped decoders check theirs, the rows are always labelled, and gtok_unremap_zinc needs its output slab.
+inline int sent_decode_zinc_check_out(const gtok_csr_built *out) { return decode_check_out(out, true); }
+inline int unremap_zinc_check(const void *ids, int32_t elem_bytes, int32_t ld, const int32_t *len, int32_t num_rows, int32_t max_num_nodes,
+                              int32_t num_node_types, const int32_t *out_ids) {
+  const int c = sent_decode_check_rows(ids, elem_bytes, ld, len, num_rows, max_num_nodes, num_node_types);
+  if (c) return c;
+  return out_ids ? GTOK_OK : GTOK_E_INVAL;
+}
 
 }  // namespace gtok

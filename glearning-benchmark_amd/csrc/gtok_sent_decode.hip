@@ -13,9 +13,14 @@
 // scatter is STABLE: inside a batch an entry's slot is its row's cursor plus the number of earlier lanes of the batch with
 // the same row, so a row lists its entries in stream order (GraphBatch.from_coo).  Everything around the parse and the
 // scatter - the slice a row claims, the row-pointer scan, `info` - is gtok_decode_csr.hpp's, shared with gtok_ibtt_decode.hip.
+//
+// ZINC-remapped rows (gtok_sent_decode_zinc_sizes / gtok_sent_decode_zinc_csr, gtok_unremap_zinc): instantiations of the same two
+// kernels that UNFOLD every chunk on the vector side before the state machine reads it (ZincUnfold), and a kernel that writes
+// the unfolded chunks out.
 #include "gtok_common.hpp"
 #include "gtok_decode_args.hpp"
 #include "gtok_decode_csr.hpp"
+#include "gtok_zinc_unremap.hpp"
 
 namespace {
 using namespace gtok;
@@ -30,27 +35,66 @@ __device__ __forceinline__ int put_lane(int s, int at, int v) { return lane_id()
 
 __device__ __forceinline__ int type_u8(int t) { return (unsigned)t < 255u ? t : 255; }   // csr.py: _to_u8
 
+// ZINC-remapped rows (include/gtok.h: the rule): one 64-token chunk UNFOLDED in registers, on the vector side.  Every lane takes the
+// preimage of its id; the folded id is told apart by the id behind it (the neighbouring lane's, or lane 0's of the next chunk,
+// which is already in flight) and by the flag `open`.  The flag is a two-state automaton over the folded ids of a row - one with an
+// edge type behind it toggles it, any other clears it - so the flag in front of a lane is the parity of the toggles below it since
+// the last clear below it (or since the chunk's start, plus the carry): two ballots and a popcount, no token taken by itself.
+struct ZincUnfold {
+  int maxn, ntypes, edge_off;
+  int open;                      // (wave-uniform) the flag in front of the next chunk
+  __device__ __forceinline__ ZincUnfold(const RowArgs &a) : maxn(a.maxn), ntypes(a.edge_off - a.node_off), edge_off(a.edge_off), open(0) {}
+  // the toggles of `tog` that count for a token with the folded ids `cb` of the clearing kind below it, and whether the carry does
+  static __device__ __forceinline__ int flag(uint64_t tog, uint64_t cb, int carry) {
+    const uint64_t since = cb ? (~0ull << (63 - __builtin_clzll(cb))) << 1 : ~0ull;     // the bits above the last clear
+    return ((int)__popcll(tog & since) + (cb ? 0 : carry)) & 1;
+  }
+  // v: the chunk's ids (lane l: token l of the `left` >= 1 ids the row still has), vn: the next chunk's.  Returns the unfolded ids
+  // (lanes at or beyond `left`: undefined) and moves `open` on.
+  __device__ __forceinline__ int chunk(int v, int vn, int left) {
+    const int lane = lane_id();
+    const bool in = lane < left;
+    const int p = zinc_pre(v, maxn, ntypes);
+    const uint64_t xs = __ballot(in && v == kZincFolded);
+    uint64_t es = __ballot(in && p >= edge_off) >> 1;                                   // bit l: an edge type stands behind token l
+    if (left > kWave && zinc_pre(__builtin_amdgcn_readfirstlane(vn), maxn, ntypes) >= edge_off) es |= 1ull << 63;
+    const uint64_t tog = xs & es, clr = xs & ~es, below = lanemask_lt();
+    const int open_here = flag(tog & below, clr & below, open);
+    open = flag(tog, clr, open);
+    if ((xs >> lane) & 1ull) return open_here ? GTOK_SENT_RADJ : ((es >> lane) & 1ull) ? GTOK_SENT_LADJ : GTOK_SENT_RESET;
+    return p != kZincNone ? p : GTOK_SENT_PAD;                                          // (PAD: no state of the parse accepts it)
+  }
+};
+
+struct NoUnfold {                // un-remapped rows: the ids as they stand
+  __device__ __forceinline__ NoUnfold(const RowArgs &) {}
+  __device__ __forceinline__ int chunk(int v, int, int) const { return v; }
+};
+
 // The state machine.  sink.node(type) is called once per node in first-visit order (type -1: none / cut), sink.edge(a, b,
-// type) once per decoded edge in stream order; everything here is wave-uniform.  Returns the status (0, 1 or 3).
+// type) once per decoded edge in stream order; everything here is wave-uniform.  Returns the status (0, 1 or 3).  ZINC: the rows are
+// ZINC-remapped - every chunk is unfolded before the state machine reads it, whose tests stay as they are.
 enum { kMain = 0, kBracket = 1, kBracketPos = 2, kNodeType = 3 };
-template <bool LAB, class Sink>
+template <bool LAB, bool ZINC, class Sink>
 __device__ __forceinline__ int parse_row(const RowArgs &a, int64_t base, int L, Sink &sink, int &num_nodes) {
   const int lane = lane_id();
   num_nodes = 0;
   if (L < 1) return 1;
   int st = 3, state = kMain, prev = -1, nseen = 0, pending = -1, k = 0, btype = -1;
   int v = lane < L ? load_id(a, base + lane) : 0;
+  std::conditional_t<ZINC, ZincUnfold, NoUnfold> zu(a);
   for (int c0 = 0; c0 < L && st == 3; c0 += kWave) {
     const int nx = c0 + kWave + lane;
     const int vn = nx < L ? load_id(a, base + nx) : 0;
     const int cn = min(kWave, L - c0);
+    const int cur = zu.chunk(v, vn, L - c0);
     int j = 0;
     if (c0 == 0) {
-      if (__builtin_amdgcn_readlane(v, 0) != GTOK_SENT_SOS) st = 1;
+      if (__builtin_amdgcn_readlane(cur, 0) != GTOK_SENT_SOS) st = 1;
       j = 1;
     }
     for (; j < cn && st == 3; ++j) {
-      const int tk = __builtin_amdgcn_readlane(v, j);
+      const int tk = __builtin_amdgcn_readlane(cur, j);
       bool new_node = false, new_edge = false;
       int ntype = -1, ea = 0, eb = 0, et = -1;
       if (state == kMain) {
@@ -111,7 +155,7 @@ struct SizesArgs {
   int units, upb;
 };
 
-template <bool LAB>
+template <bool LAB, bool ZINC = false>
 __global__ void __launch_bounds__(256) sent_decode_sizes_kernel(const SizesArgs a) {
   const int wave = wave_id(), wpb = (int)(blockDim.x >> 6);
   const int vb = virtual_block();
@@ -122,7 +166,7 @@ __global__ void __launch_bounds__(256) sent_decode_sizes_kernel(const SizesArgs 
     int64_t base; int L, n;
     row_span(a.r, r, base, L);
     CountSink sink;
-    const int st = parse_row<LAB>(a.r, base, L, sink, n);
+    const int st = parse_row<LAB, ZINC>(a.r, base, L, sink, n);
     if (lane_id() == 0) {
       a.num_nodes[r] = st == 1 ? 0 : n;
       a.num_entries[r] = st == 1 ? 0 : sink.entries;
@@ -234,7 +278,7 @@ struct CsrArgs {
   int units, upb;
 };
 
-template <bool LAB>
+template <bool LAB, bool ZINC = false>
 __global__ void __launch_bounds__(256) sent_decode_csr_kernel(const CsrArgs a) {
   extern __shared__ __align__(16) unsigned char smem[];
   const int lane = lane_id();
@@ -261,7 +305,7 @@ __global__ void __launch_bounds__(256) sent_decode_csr_kernel(const CsrArgs a) {
     DegreeSink<LAB> ds;
     ds.deg = deg; ds.ncl = ncl;
     ds.stage_pk = stage_pk; ds.stage_t = stage_t; ds.stage_nt = stage_nt; ds.cap = a.cap; ds.ncap = ncap;
-    const int st = parse_row<LAB>(a.r, base, L, ds, n);
+    const int st = parse_row<LAB, ZINC>(a.r, base, L, ds, n);
     ds.flush();
     if (LAB) ds.flush_nodes();
     wave_sync();
@@ -287,12 +331,47 @@ __global__ void __launch_bounds__(256) sent_decode_csr_kernel(const CsrArgs a) {
         for (int u = lane; u < n; u += kWave) ss.nattr[u] = stage_nt[u];
     } else {
       int n2;
-      (void)parse_row<LAB>(a.r, base, L, ss, n2);
+      (void)parse_row<LAB, ZINC>(a.r, base, L, ss, n2);
       ss.flush();
       if (LAB) ss.flush_nodes();
     }
   }
   acc.report(a.out.info);
+}
+
+// ---- gtok_unremap_zinc: the unfolded ids of every row as an int32 slab, `pad` behind them --------------------------------------
+struct UnremapArgs {
+  RowArgs r;
+  int32_t *out;
+  int pad;
+  int units, upb;
+};
+
+__global__ void __launch_bounds__(256) unremap_zinc_kernel(const UnremapArgs a) {
+  const int lane = lane_id();
+  const int wave = wave_id(), wpb = (int)(blockDim.x >> 6);
+  const int vb = virtual_block();
+  const int u0 = vb * a.upb, u1 = min(a.units, u0 + a.upb);
+  for (int unit = u0; unit < u1; ++unit) {
+    const int r = unit * wpb + wave;
+    if (r >= a.r.rows) break;
+    int64_t base; int L;
+    row_span(a.r, r, base, L);
+    int32_t *row = a.out + (int64_t)r * a.r.ld;
+    ZincUnfold zu(a.r);
+    int v = lane < L ? load_id(a.r, base + lane) : 0;
+    for (int64_t c0 = 0; c0 < a.r.ld; c0 += kWave) {          // (64-bit: c0 + 64 may pass 2^31 where ld is close to it)
+      const int64_t i = c0 + lane;
+      int vn = 0, u = a.pad;
+      if (c0 < L) {
+        vn = i + kWave < L ? load_id(a.r, base + i + kWave) : 0;
+        u = zu.chunk(v, vn, L - (int)c0);
+        if (i >= L) u = a.pad;
+      }
+      if (i < a.r.ld) row[i] = u;
+      v = vn;
+    }
+  }
 }
 
 RowArgs row_args(const void *ids, int32_t elem_bytes, const int64_t *row_start, int32_t ld, const int32_t *len, int32_t num_rows,
@@ -303,26 +382,26 @@ RowArgs row_args(const void *ids, int32_t elem_bytes, const int64_t *row_start, 
   return r;
 }
 
-}  // namespace
+// the kernel of a row kind: ZINC-remapped rows (always labelled), labelled, unlabelled
+template <class K> K pick(bool zinc, bool labeled, K z, K l, K u) { return zinc ? z : labeled ? l : u; }
 
-extern "C" int gtok_sent_decode_sizes(const void *ids, int32_t elem_bytes, const int64_t *row_start, int32_t ld, const int32_t *len,
-                                      int32_t num_rows, int32_t max_num_nodes, int32_t labeled, int32_t num_node_types,
-                                      int32_t *num_nodes, int32_t *num_entries, int32_t *status, void *stream) {
+int decode_sizes(const void *ids, int32_t elem_bytes, const int64_t *row_start, int32_t ld, const int32_t *len, int32_t num_rows,
+                 int32_t max_num_nodes, bool labeled, bool zinc, int32_t num_node_types, int32_t *num_nodes, int32_t *num_entries,
+                 int32_t *status, void *stream) {
   const int c = sent_decode_check_rows(ids, elem_bytes, ld, len, num_rows, max_num_nodes, num_node_types);
   return decode_launch(c, num_nodes && num_entries && status, nullptr, stream, [&](int dev, hipStream_t s) {
     SizesArgs a;
     a.r = row_args(ids, elem_bytes, row_start, ld, len, num_rows, max_num_nodes, num_node_types);
     a.num_nodes = num_nodes; a.num_entries = num_entries; a.status = status;
-    return labeled ? launch_wave_per_item(sent_decode_sizes_kernel<true>, a, num_rows, 4, 0, dev, s)
-                   : launch_wave_per_item(sent_decode_sizes_kernel<false>, a, num_rows, 4, 0, dev, s);
+    const auto kern = pick(zinc, labeled, sent_decode_sizes_kernel<true, true>, sent_decode_sizes_kernel<true>, sent_decode_sizes_kernel<false>);
+    return launch_wave_per_item(kern, a, num_rows, 4, 0, dev, s);
   });
 }
 
-extern "C" int gtok_sent_decode_csr(const void *ids, int32_t elem_bytes, const int64_t *row_start, int32_t ld, const int32_t *len,
-                                    int32_t num_rows, int32_t max_num_nodes, int32_t labeled, int32_t num_node_types,
-                                    const gtok_csr_built *out, void *stream) {
+int decode_csr(const void *ids, int32_t elem_bytes, const int64_t *row_start, int32_t ld, const int32_t *len, int32_t num_rows,
+               int32_t max_num_nodes, bool labeled, bool zinc, int32_t num_node_types, const gtok_csr_built *out, void *stream) {
   const int c = sent_decode_check_rows(ids, elem_bytes, ld, len, num_rows, max_num_nodes, num_node_types);
-  return decode_launch(c, sent_decode_check_out(out, labeled) == GTOK_OK, out, stream, [&](int dev, hipStream_t s) {
+  return decode_launch(c, (zinc ? sent_decode_zinc_check_out(out) : sent_decode_check_out(out, labeled)) == GTOK_OK, out, stream, [&](int dev, hipStream_t s) {
     CsrArgs a;
     a.r = row_args(ids, elem_bytes, row_start, ld, len, num_rows, max_num_nodes, num_node_types);
     a.out = *out;
@@ -334,7 +413,48 @@ extern "C" int gtok_sent_decode_csr(const void *ids, int32_t elem_bytes, const i
     int stage_bytes = a.cap * 4 + (labeled ? a.cap + align_up(max_num_nodes, 16) : 0);
     if (a.deg_bytes + stage_bytes > kLdsWithoutOptIn) { a.cap = 0; stage_bytes = 0; }
     a.stride = a.deg_bytes + stage_bytes;
-    return labeled ? launch_wave_per_item(sent_decode_csr_kernel<true>, a, num_rows, 4, a.stride, dev, s)
-                   : launch_wave_per_item(sent_decode_csr_kernel<false>, a, num_rows, 4, a.stride, dev, s);
+    const auto kern = pick(zinc, labeled, sent_decode_csr_kernel<true, true>, sent_decode_csr_kernel<true>, sent_decode_csr_kernel<false>);
+    return launch_wave_per_item(kern, a, num_rows, 4, a.stride, dev, s);
+  });
+}
+
+}  // namespace
+
+extern "C" int gtok_sent_decode_sizes(const void *ids, int32_t elem_bytes, const int64_t *row_start, int32_t ld, const int32_t *len,
+                                      int32_t num_rows, int32_t max_num_nodes, int32_t labeled, int32_t num_node_types,
+                                      int32_t *num_nodes, int32_t *num_entries, int32_t *status, void *stream) {
+  return decode_sizes(ids, elem_bytes, row_start, ld, len, num_rows, max_num_nodes, labeled != 0, false, num_node_types, num_nodes, num_entries,
+                      status, stream);
+}
+
+extern "C" int gtok_sent_decode_csr(const void *ids, int32_t elem_bytes, const int64_t *row_start, int32_t ld, const int32_t *len,
+                                    int32_t num_rows, int32_t max_num_nodes, int32_t labeled, int32_t num_node_types,
+                                    const gtok_csr_built *out, void *stream) {
+  return decode_csr(ids, elem_bytes, row_start, ld, len, num_rows, max_num_nodes, labeled != 0, false, num_node_types, out, stream);
+}
+
+// ---- ZINC-remapped rows (include/gtok.h)
+extern "C" int gtok_sent_decode_zinc_sizes(const void *ids, int32_t elem_bytes, const int64_t *row_start, int32_t ld, const int32_t *len,
+                                           int32_t num_rows, int32_t max_num_nodes, int32_t num_node_types, int32_t *num_nodes,
+                                           int32_t *num_entries, int32_t *status, void *stream) {
+  return decode_sizes(ids, elem_bytes, row_start, ld, len, num_rows, max_num_nodes, true, true, num_node_types, num_nodes, num_entries, status,
+                      stream);
+}
+
+extern "C" int gtok_sent_decode_zinc_csr(const void *ids, int32_t elem_bytes, const int64_t *row_start, int32_t ld, const int32_t *len,
+                                         int32_t num_rows, int32_t max_num_nodes, int32_t num_node_types, const gtok_csr_built *out,
+                                         void *stream) {
+  return decode_csr(ids, elem_bytes, row_start, ld, len, num_rows, max_num_nodes, true, true, num_node_types, out, stream);
+}
+
+extern "C" int gtok_unremap_zinc(const void *ids, int32_t elem_bytes, const int64_t *row_start, int32_t ld, const int32_t *len,
+                                 int32_t num_rows, int32_t max_num_nodes, int32_t num_node_types, int32_t pad_id, int32_t *out_ids,
+                                 void *stream) {
+  const int c = unremap_zinc_check(ids, elem_bytes, ld, len, num_rows, max_num_nodes, num_node_types, out_ids);
+  return decode_launch(c, true, nullptr, stream, [&](int dev, hipStream_t s) {
+    UnremapArgs a;
+    a.r = row_args(ids, elem_bytes, row_start, ld, len, num_rows, max_num_nodes, num_node_types);
+    a.out = out_ids; a.pad = pad_id;
+    return launch_wave_per_item(unremap_zinc_kernel, a, num_rows, 4, 0, dev, s);
   });
 }

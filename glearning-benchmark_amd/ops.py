@@ -949,6 +949,72 @@ def sent_decode_csr(ids: torch.Tensor, ln: torch.Tensor, max_num_nodes: int, lab
 
 
 # ------------------------------------------------------------------------------------------------
+# ZINC-remapped SENT rows -> ids / CSR (include/gtok.h: gtok_unremap_zinc, gtok_sent_decode_zinc_sizes / gtok_sent_decode_zinc_csr)
+# ------------------------------------------------------------------------------------------------
+_ZINC_WHAT = "gtok_unremap_zinc / gtok_sent_decode_zinc_sizes / gtok_sent_decode_zinc_csr"
+
+
+def unremap_zinc(ids: torch.Tensor, ln: torch.Tensor, max_num_nodes: int, num_node_types: int, row_start: Optional[torch.Tensor] = None,
+                 ld: Optional[int] = None, pad_id: int = SENT_PAD) -> torch.Tensor:
+    """gtok_unremap_zinc: ZINC-remapped labelled SENT rows (sent(..., remap_zinc=True)) -> int32 [rows, ld], row r its first
+    min(len, ld) ids UNFOLDED to the raw ids of the same walk (include/gtok.h: the rule), pad_id behind them.  max_num_nodes /
+    num_node_types: the walk's own.  ids / row_start as sent_decode_csr; with row_start (packed rows) ld - the width of the
+    result - must be given.  Only the last id of a row that a cut leaves ending in the folded id can differ from the walk's raw
+    row (RESET where it wrote LADJ).  Nothing is read back."""
+    if row_start is not None and ld is None:
+        raise ValueError("unremap_zinc: with row_start, ld (the width of the result) must be given")
+    eb, ld, rows = _decode_rows(ids, ln, row_start, ld, "unremap_zinc")
+    _need(_lib.ZINC_DECODE_SYMBOLS, _ZINC_WHAT)
+    out = torch.empty((rows, ld), dtype=torch.int32, device=ids.device)
+    if rows:
+        check(lib().gtok_unremap_zinc(ids.data_ptr(), eb, None if row_start is None else row_start.data_ptr(), ld, ln.data_ptr(), rows,
+                                      int(max_num_nodes), int(num_node_types), int(pad_id), out.data_ptr(), _stream(ids.device)),
+              "gtok_unremap_zinc")
+    return out
+
+
+def sent_decode_zinc_sizes(ids: torch.Tensor, ln: torch.Tensor, max_num_nodes: int, num_node_types: int,
+                           row_start: Optional[torch.Tensor] = None, ld: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """gtok_sent_decode_zinc_sizes: sent_decode_sizes for ZINC-remapped labelled rows."""
+    eb, ld, rows = _decode_rows(ids, ln, row_start, ld, "sent_decode_zinc_sizes")
+    _need(_lib.ZINC_DECODE_SYMBOLS, _ZINC_WHAT)
+    dev = ids.device
+    nn, ne, st = (torch.empty(rows, dtype=torch.int32, device=dev) for _ in range(3))
+    if rows:
+        check(lib().gtok_sent_decode_zinc_sizes(ids.data_ptr(), eb, None if row_start is None else row_start.data_ptr(), ld, ln.data_ptr(), rows,
+                                                int(max_num_nodes), int(num_node_types), nn.data_ptr(), ne.data_ptr(), st.data_ptr(),
+                                                _stream(dev)), "gtok_sent_decode_zinc_sizes")
+    return nn, ne, st
+
+
+def _decode_zinc_csr_launch(ids, ln, row_start, ld, max_num_nodes, num_node_types, node_ptr, edge_ptr, N: int, E: int) -> dict:
+    """gtok_sent_decode_zinc_csr on the current stream into fresh arrays of the given totals: -> dict of gtok_csr_built's arrays;
+    no host read."""
+    eb, ld, rows = _decode_rows(ids, ln, row_start, ld, "sent_decode_zinc_csr")
+    _need(_lib.ZINC_DECODE_SYMBOLS, _ZINC_WHAT)
+    dev = ids.device
+    o, cout = _built_arrays("sent_decode_zinc_csr", dev, rows, N, E, True, True, node_ptr, edge_ptr)
+    if rows == 0:
+        return o
+    check(lib().gtok_sent_decode_zinc_csr(ids.data_ptr(), eb, None if row_start is None else row_start.data_ptr(), ld, ln.data_ptr(), rows,
+                                          int(max_num_nodes), int(num_node_types), ctypes.byref(cout), _stream(dev)),
+          "gtok_sent_decode_zinc_csr")
+    return o
+
+
+def sent_decode_zinc_csr(ids: torch.Tensor, ln: torch.Tensor, max_num_nodes: int, num_node_types: int,
+                         row_start: Optional[torch.Tensor] = None, check_symmetric: bool = False,
+                         ld: Optional[int] = None) -> Tuple[GraphBatch, torch.Tensor]:
+    """ZINC-remapped labelled SENT rows (sent(..., remap_zinc=True): what every ZINC run trains on) -> (GraphBatch, status int32
+    [rows]): sent_decode_csr over the unfolded rows (unremap_zinc), the unfold done in registers while the row is parsed.  The
+    result is that of sent_decode_csr over the raw rows of the same walk; a damaged row decodes as its unfolded ids do.  Ids behind
+    EOS (a query tail) are not parsed.  ids / row_start / ld / check_symmetric and the read-backs as sent_decode_csr."""
+    nn, ne, status = sent_decode_zinc_sizes(ids, ln, max_num_nodes, num_node_types, row_start, ld)
+    launch = lambda node_ptr, edge_ptr, N, E: _decode_zinc_csr_launch(ids, ln, row_start, ld, max_num_nodes, num_node_types, node_ptr, edge_ptr, N, E)
+    return _decoded_batch("sent_decode_zinc_csr", nn, ne, launch, check_symmetric), status
+
+
+# ------------------------------------------------------------------------------------------------
 # IBTT rows -> CSR (include/gtok.h: gtok_ibtt_decode_sizes / gtok_ibtt_decode_csr)
 # ------------------------------------------------------------------------------------------------
 IBTT_GRAMMARS = {"zinc": _lib.IBTT_GRAMMAR_ZINC, "synth": _lib.IBTT_GRAMMAR_SYNTH}

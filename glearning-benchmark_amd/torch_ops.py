@@ -541,6 +541,51 @@ def _(ids, lens, max_num_nodes, labeled, num_node_types, node_ptr, edge_ptr, tot
             e(total_nodes if labeled else 0, torch.uint8), e(total_entries if labeled else 0, torch.uint8), e(8, torch.int32))
 
 
+@torch.library.custom_op("gtok::unremap_zinc", mutates_args=(), device_types="cuda")
+def unremap_zinc(ids: Tensor, lens: Tensor, max_num_nodes: int, num_node_types: int, row_start: Optional[Tensor] = None, ld: int = 0,
+                 pad_id: int = 5) -> Tensor:
+    """gtok_unremap_zinc: ZINC-remapped labelled SENT rows -> int32 [rows, ld] of the unfolded (raw) ids, pad_id behind them; ids /
+    row_start as gtok::sent_decode_sizes; ld = 0: the slab's width (packed rows need an ld)."""
+    return _ops.unremap_zinc(ids, lens, max_num_nodes, num_node_types, row_start, ld if ld > 0 else None, pad_id)
+
+
+@unremap_zinc.register_fake
+def _(ids, lens, max_num_nodes, num_node_types, row_start=None, ld=0, pad_id=5):
+    return ids.new_empty((lens.shape[0], ld if ld > 0 else ids.shape[-1]), dtype=torch.int32)
+
+
+@torch.library.custom_op("gtok::sent_decode_zinc_sizes", mutates_args=(), device_types="cuda")
+def sent_decode_zinc_sizes(ids: Tensor, lens: Tensor, max_num_nodes: int, num_node_types: int,
+                           row_start: Optional[Tensor] = None, ld: int = 0) -> Tuple[Tensor, Tensor, Tensor]:
+    """gtok_sent_decode_zinc_sizes: gtok::sent_decode_sizes for ZINC-remapped labelled rows."""
+    return _ops.sent_decode_zinc_sizes(ids, lens, max_num_nodes, num_node_types, row_start, ld if ld > 0 else None)
+
+
+@sent_decode_zinc_sizes.register_fake
+def _(ids, lens, max_num_nodes, num_node_types, row_start=None, ld=0):
+    i32 = lambda: ids.new_empty((lens.shape[0],), dtype=torch.int32)
+    return i32(), i32(), i32()
+
+
+@torch.library.custom_op("gtok::sent_decode_zinc_csr", mutates_args=(), device_types="cuda")
+def sent_decode_zinc_csr(ids: Tensor, lens: Tensor, max_num_nodes: int, num_node_types: int, node_ptr: Tensor, edge_ptr: Tensor,
+                         total_nodes: int, total_entries: int, row_start: Optional[Tensor] = None,
+                         ld: int = 0) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """gtok_sent_decode_zinc_csr: gtok::sent_decode_csr for ZINC-remapped labelled rows -> (rowptr int32 [N + rows], col int32 [E],
+    eorder int32 [E], nattr uint8 [N], eattr uint8 [E], info int32 [8]).  Nothing is read back."""
+    o = _ops._decode_zinc_csr_launch(ids, lens, row_start, ld if ld > 0 else None, max_num_nodes, num_node_types, node_ptr, edge_ptr,
+                                     total_nodes, total_entries)
+    return o["rowptr"], o["col"], o["eorder"], o["nattr"], o["eattr"], o["info"]
+
+
+@sent_decode_zinc_csr.register_fake
+def _(ids, lens, max_num_nodes, num_node_types, node_ptr, edge_ptr, total_nodes, total_entries, row_start=None, ld=0):
+    rows = lens.shape[0]
+    e = lambda n, dt: ids.new_empty((n,), dtype=dt)
+    return (e(total_nodes + rows, torch.int32), e(total_entries, torch.int32), e(total_entries, torch.int32),
+            e(total_nodes, torch.uint8), e(total_entries, torch.uint8), e(8, torch.int32))
+
+
 @torch.library.custom_op("gtok::ibtt_decode_sizes", mutates_args=(), device_types="cuda")
 def ibtt_decode_sizes(ids: Tensor, lens: Tensor, grammar: int, inv: Tensor, max_num_nodes: int,
                       row_start: Optional[Tensor] = None, ld: int = 0) -> Tuple[Tensor, Tensor, Tensor, Tensor]:

@@ -24,6 +24,8 @@
  *   gtok_sent_decode   the SENT spec read backwards (token rows -> graphs in visit-index space)
  *   gtok_sent_decode_sizes / gtok_sent_decode_csr   the same, from int32 / 16-bit slabs or packed rows, a wave per row, into a
  *                      batched CSR (gtok_csr's arrays): what a generative model's sequences are turned back into
+ *   gtok_unremap_zinc / gtok_sent_decode_zinc_sizes / gtok_sent_decode_zinc_csr   the way back from ZINC-REMAPPED labelled rows (what
+ *                      every ZINC run trains on): the raw ids of the same walk, and the decoders above over them
  *   gtok_remap_zinc    trainer/train_agtt.py:171-244 on an existing token slab
  *   gtok_collate       data_loader.py:488-497 and trainer/train_agtt.py:276-302
  *                      (gather rows of a batch, pad to the batch max, bool mask)
@@ -706,7 +708,7 @@ int gtok_sent_decode(const int32_t *ids, int32_t ld, const int32_t *len, int32_t
  * Rows: row r = the first min(len[r], ld) ids at element row_start[r] of `ids` (row_start NULL: at r * ld - a [rows, ld] slab
  * read in place), elem_bytes 1, 2 or 4 bytes each: an int32 slab, a GTOK_SENT_U16 slab, or packed rows (gtok_pack_rows_scan's
  * row_ptr, gtok_sent_packed's row_start); a negative row_start = an empty row.  Un-remapped SENT ids only (remap_zinc folds
- * RESET, LADJ and RADJ into one id).  4-byte ids are read as int32, as gtok_sent_decode reads them.
+ * RESET, LADJ and RADJ into one id: gtok_sent_decode_zinc_sizes / gtok_sent_decode_zinc_csr below read those).  4-byte ids are read as int32, as gtok_sent_decode reads them.
  * One row becomes one graph, in visit-index space.  status[r], the node count and the edge list are those of gtok_sent_decode's
  * state machine with unlimited capacities (status 2 cannot occur).  A status-1 row (malformed, len < 1, a negative start) is an
  * EMPTY graph (N = 0, E = 0): rows and graphs stay index-aligned.  A status-3 row (cut before EOS) gives the part of the graph
@@ -738,6 +740,46 @@ int gtok_sent_decode_sizes(const void *ids, int32_t elem_bytes, const int64_t *r
 int gtok_sent_decode_csr(const void *ids, int32_t elem_bytes, const int64_t *row_start, int32_t ld, const int32_t *len,
                          int32_t num_rows, int32_t max_num_nodes, int32_t labeled, int32_t num_node_types,
                          const gtok_csr_built *out, void *stream);
+
+/* ---- ZINC-remapped SENT rows back to raw ids and to a batched CSR ---------------------------------------------------------------
+ * gtok_sent with remap_zinc = 1 (every ZINC run of the reference: trainer/train_agtt.py:171-244) folds RESET, LADJ and RADJ into
+ * one id.  For LABELLED rows - the only ones the remap is used on - the fold is undone with one id of look-ahead and one bit of
+ * state: every trail step and every bracket member starts with an edge-type id, and a RESET is always followed by a position.
+ * Parameters (the walk's own): M = max_num_nodes, T = num_node_types, idx_off = 6, node_off = 6 + M, edge_off = node_off + T.
+ * Preimage.  The remap (remap_zinc_token; csrc/gtok_zinc_unremap.hpp restates it beside this inverse) is injective on raw ids
+ * t >= 0 outside {1, 2, 3, 5}; pre(id) is the one such t whose remap is id, or "none":
+ *   0 -> SOS (0), 1 -> EOS (4); 8..16 -> node_off + (id - 8); 17..20 -> edge_off + (id - 17); 22..22+M-1 -> idx_off + (id - 22);
+ *   id >= 22 + node_off -> id - 22; a candidate counts only if remapping it gives id back (8 + a with a >= T has none, nor has
+ *   22 + t for an atom or bond t that has an id of its own); 3..7, 21, negative ids and everything else: none.  2 is the folded id X.
+ * Unfold.  The first min(len, ld) ids of a row, left to right, with a flag open = 0:
+ *   at an X with open set: RADJ (3), open cleared; else, when a next id exists inside the row and its preimage is >= edge_off:
+ *   LADJ (2), open set; else RESET (1).  Any other id becomes its preimage; an id without one becomes PAD (5), which no state of
+ *   the decoder accepts.
+ * Decode.  decode_zinc(row) = the labelled decoder of gtok_sent_decode_sizes / gtok_sent_decode_csr over unfold(row): status, node
+ * count, edge list, types and the CSR are thereby defined for every input, damaged rows included.  Consequences:
+ *   - unfolding a remapped row gives the raw row of the same walk id for id, except that a row which a cut leaves ENDING in X gets
+ *     RESET there where the walk may have written LADJ - nothing decodable differs;
+ *   - ids behind EOS (a query tail) are unfolded but never parsed, as in the un-remapped decoders;
+ *   - UNLABELLED remapped rows are ambiguous (position X position) and have no entry point.
+ * gtok_unremap_zinc: rows read exactly as gtok_sent_decode_csr reads them (elem_bytes 1 / 2 / 4, row_start, ld, len; a negative start
+ * or len < 1: an empty row); out_ids int32 [num_rows, ld] (must not overlap ids): row r = its unfolded ids, then pad_id to the end of
+ * the row.  A wave per row on the vector side: 64 ids per step, the look-ahead from the neighbouring lane (or lane 0 of the next
+ * chunk), the flag - a two-state automaton over the X's: one with an edge type behind it toggles it, any other clears it - from two
+ * ballots, one bit carried between chunks.
+ * gtok_sent_decode_zinc_sizes / gtok_sent_decode_zinc_csr: gtok_sent_decode_sizes / gtok_sent_decode_csr without `labeled` (always
+ * 1: out->nattr / out->eattr are needed); outputs, info[8], the slice checks and the errors are theirs.  Every 64-id chunk is
+ * unfolded in registers before the state machine reads it.
+ * Errors, before anything is launched or written: those of gtok_sent_decode_csr (GTOK_E_TOO_LARGE for max_num_nodes >
+ * GTOK_SENT_LARGE_MAX_NODES included), GTOK_E_INVAL for a NULL out_ids; num_rows == 0 is a no-op.  The calls only enqueue on
+ * `stream` (capturable).  (Added without an ABI version step: no struct changes.)                                                  */
+int gtok_unremap_zinc(const void *ids, int32_t elem_bytes, const int64_t *row_start, int32_t ld, const int32_t *len, int32_t num_rows,
+                      int32_t max_num_nodes, int32_t num_node_types, int32_t pad_id, int32_t *out_ids, void *stream);
+int gtok_sent_decode_zinc_sizes(const void *ids, int32_t elem_bytes, const int64_t *row_start, int32_t ld, const int32_t *len,
+                                int32_t num_rows, int32_t max_num_nodes, int32_t num_node_types,
+                                int32_t *num_nodes, int32_t *num_entries, int32_t *status, void *stream);
+int gtok_sent_decode_zinc_csr(const void *ids, int32_t elem_bytes, const int64_t *row_start, int32_t ld, const int32_t *len,
+                              int32_t num_rows, int32_t max_num_nodes, int32_t num_node_types,
+                              const gtok_csr_built *out, void *stream);
 
 /* ---- IBTT rows back to a batched CSR: the same two passes, outputs and row formats as the SENT pair above ---------------------
  * Rows: exactly as gtok_sent_decode_csr reads them (row_start / ld / len / elem_bytes; a negative start or fewer than one id:
