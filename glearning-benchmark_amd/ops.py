@@ -1216,6 +1216,113 @@ def graphs_equal(a: GraphBatch, b: GraphBatch) -> torch.Tensor:
     return same
 
 
+# ------------------------------------------------------------------------------------------------
+# the task answers of a batch (include/gtok.h: gtok_graph_tasks): cycle check, components, shortest-path distances
+# ------------------------------------------------------------------------------------------------
+TASKS_MAX_NODES_ANY = 512      # beyond it gtok_graph_tasks searches the CSR itself and needs GTOK_CSR_SIMPLE_SYMMETRIC
+TASKS_BAD_QUERY, TASKS_DAMAGED = 1, 2       # info[0] bits
+
+
+class GraphTasks:
+    """What ops.graph_tasks returns, all device tensors: has_cycle int32 [G] (1 / 0), num_components int32 [G], dist int32 [Q] (None
+    without queries; -1 unreachable, -2 an endpoint outside its graph), info int32 [4].  Nothing is read back unless status() is
+    called."""
+    __slots__ = ("has_cycle", "num_components", "dist", "info")
+
+    def __init__(self, has_cycle, num_components, dist, info):
+        self.has_cycle, self.num_components, self.dist, self.info = has_cycle, num_components, dist, info
+
+    def status(self) -> Dict[str, int]:
+        """One 16-byte read-back of info: status bits (TASKS_BAD_QUERY, TASKS_DAMAGED), the largest distance, the queries answered
+        -1, the graphs with a cycle."""
+        v = self.info.tolist()
+        return dict(status=v[0], max_dist=v[1], unreachable=v[2], cycles=v[3])
+
+
+def _graph_tasks_launch(batch: GraphBatch, queries: Optional[torch.Tensor], query_ptr: Optional[torch.Tensor], has_cycle: bool = True,
+                        num_components: bool = True):
+    """gtok_graph_tasks on the current stream into fresh arrays -> (has_cycle, num_components, dist, info), None for what was not
+    asked for; no host read."""
+    _need_gpu(batch.col, "graph_tasks")
+    _need(_lib.GRAPH_TASKS_SYMBOLS, "gtok_graph_tasks")
+    dev, G = batch.device, batch.num_graphs
+    if batch.max_nodes > _lib.SENT_LARGE_MAX_NODES:
+        raise _lib.GtokError(f"graph_tasks: a graph of {batch.max_nodes} nodes is beyond the {_lib.SENT_LARGE_MAX_NODES} the search holds in LDS "
+                             "(GTOK_E_TOO_LARGE)")
+    if batch.max_nodes > TASKS_MAX_NODES_ANY and not (batch.flags & _lib.CSR_SIMPLE_SYMMETRIC):
+        raise _lib.GtokError(f"graph_tasks: graphs of more than {TASKS_MAX_NODES_ANY} nodes (this batch: {batch.max_nodes}) are searched over the CSR "
+                             "itself, which must list every edge once in each direction, without loops: the batch does not carry "
+                             "GTOK_CSR_SIMPLE_SYMMETRIC (build it with check_symmetric=True from a both-directions edge list) (GTOK_E_UNSUPPORTED)")
+    if batch.graph_ids is not None:
+        raise ValueError("graph_tasks: a batch in dataset order only (not ops.lane_sorted's copy)")
+    i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
+    cyc, comp = (i32(G) if has_cycle else None), (i32(G) if num_components else None)
+    info = torch.zeros(4, dtype=torch.int32, device=dev)
+    dist = None
+    if queries is None:
+        if query_ptr is not None:
+            raise ValueError("graph_tasks: query_ptr without queries")
+        Q = 0
+    else:
+        queries = queries.to(dev, dtype=torch.int32).contiguous()
+        if queries.dim() != 2 or queries.shape[1] != 2:
+            raise ValueError("graph_tasks: queries must be [Q, 2] (local node ids)")
+        Q = int(queries.shape[0])
+        if query_ptr is None:
+            if Q != G:
+                raise ValueError(f"graph_tasks: without query_ptr there is exactly one query per graph ({G}), got {Q}")
+        else:
+            query_ptr = query_ptr.to(dev, dtype=torch.int64).contiguous().reshape(-1)
+            if int(query_ptr.numel()) != G + 1:
+                raise ValueError("graph_tasks: query_ptr must be [G + 1]")
+        if G == 0 and Q:
+            raise ValueError("graph_tasks: queries but no graphs")
+        dist = i32(Q)
+    if G == 0 or not (has_cycle or num_components or queries is not None):
+        return cyc, comp, dist, info
+    p = lambda t: None if t is None else t.data_ptr()
+    qn = queries if (queries is None or Q) else torch.empty((1, 2), dtype=torch.int32, device=dev)    # (an empty tensor's pointer may be null)
+    dd = dist if (dist is None or Q) else i32(1)
+    cs = batch.c_struct()
+    check(lib().gtok_graph_tasks(ctypes.byref(cs), p(qn), p(query_ptr), Q, p(cyc), p(comp), p(dd), info.data_ptr(), _stream(dev)),
+          "gtok_graph_tasks")
+    return cyc, comp, dist, info
+
+
+def graph_tasks(batch: GraphBatch, queries: Optional[torch.Tensor] = None, query_ptr: Optional[torch.Tensor] = None,
+                has_cycle: bool = True, num_components: bool = True) -> GraphTasks:
+    """gtok_graph_tasks: the answers of the two graph-token tasks for every graph of the batch, on the device -> GraphTasks.  The
+    graph of a CSR slice is the simple undirected closure of its entries (one direction or both, duplicates and self loops allowed up
+    to 512 nodes; larger graphs need a GTOK_CSR_SIMPLE_SYMMETRIC batch).  queries int32 [Q, 2] local node ids, graph g's at
+    query_ptr[g] .. query_ptr[g + 1] (int64 [G + 1]; None: one per graph, the tensor ops.sent(query=) takes).  Labels of the
+    reference are host arithmetic on top: `lenK` <-> dist - 1, dist <= 0 = the item is dropped."""
+    return GraphTasks(*_graph_tasks_launch(batch, queries, query_ptr, has_cycle, num_components))
+
+
+def check_task_labels(batch: GraphBatch, task: str, labels: torch.Tensor, query_nodes: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """bool [G]: records whose stored label disagrees with their graph - the device version of the reference's consistency script
+    (test/data_distribution_test.py:136-140) behind ops.parse_graph_texts -> GraphBatch.from_coo_device.  labels int32 [G] in
+    gtok_parse_graph_text's conventions: cycle_check 1 / 0, shortest_path K - 1 for `lenK`; NO_LABEL = none, never a disagreement.
+    query_nodes int32 [G, 2] (shortest_path), (-1, -1) = none, never a disagreement; a labelled pair that is unreachable, equal or
+    outside its graph disagrees with any label."""
+    if task not in ("cycle_check", "shortest_path"):
+        raise ValueError('task must be "cycle_check" or "shortest_path"')
+    dev = batch.device
+    labels = labels.to(dev, dtype=torch.int32).reshape(-1)
+    if int(labels.numel()) != batch.num_graphs:
+        raise ValueError("check_task_labels: one label per graph")
+    has = labels != NO_LABEL
+    if task == "cycle_check":
+        r = graph_tasks(batch, num_components=False)
+        return has & (r.has_cycle != labels)
+    if query_nodes is None:
+        raise ValueError("check_task_labels: shortest_path needs query_nodes [G, 2]")
+    query_nodes = query_nodes.to(dev, dtype=torch.int32).reshape(-1, 2)
+    r = graph_tasks(batch, query_nodes, has_cycle=False, num_components=False)
+    asked = ~((query_nodes[:, 0] == -1) & (query_nodes[:, 1] == -1))
+    return has & asked & ((r.dist - 1) != labels)
+
+
 def remap_zinc(ids: torch.Tensor, ln: torch.Tensor, idx_offset: int, node_idx_offset: int,
                edge_idx_offset: int) -> torch.Tensor:
     _need_gpu(ids, "remap_zinc")

@@ -304,6 +304,40 @@ def mix_batch_device(num_graphs: int, device, seed: int = 0, min_nodes: int = 10
                 src=cat(srcs).astype(np.int64), dst=cat(dsts).astype(np.int64), family=fam.cpu().numpy())
 
 
+def label_batch_device(batch, task: str, seed: int = 0, pairs_per_graph: int = 1) -> Dict[str, object]:
+    """Task labels (and query pairs) for a batch that lives on the GPU - what graph_token_like() computes per graph on the host
+    (_has_cycle, _bfs_dist), as one launch of ops.graph_tasks; nothing is copied back.  Returns device tensors:
+      cycle_check    labels int32 [G]: 1 / 0
+      shortest_path  queries int32 [Q, 2] (Q = G * pairs_per_graph, graph by graph): pairs u != v drawn from a torch.Generator seeded
+                     with `seed` on the batch's device ((-1, -1) for a graph of fewer than 2 nodes: its dist is -2, keep False); graph_index int64 [Q]; query_ptr
+                     int64 [G + 1]; dist int32 [Q]; labels = dist - 1 (`lenK` <-> K - 1); keep bool [Q] = dist > 0 (the reference
+                     drops INF items).  With pairs_per_graph = 1, `queries` is what ops.sent(query=) / ops.ibtt_synth(query=) take.
+    The graph of a CSR slice is the simple undirected closure of its entries (include/gtok.h: gtok_graph_tasks), so one-direction
+    edge lists - er_batch_device, mix_batch_device - are labelled as they are."""
+    import torch
+    from . import ops
+    if task == "cycle_check":
+        return dict(labels=ops.graph_tasks(batch, num_components=False).has_cycle)
+    if task != "shortest_path":
+        raise ValueError('task must be "cycle_check" or "shortest_path"')
+    if pairs_per_graph < 1:
+        raise ValueError("pairs_per_graph must be at least 1")
+    dev, G = batch.device, batch.num_graphs
+    gen = torch.Generator(device=dev); gen.manual_seed(int(seed))
+    graph_index = torch.arange(G, device=dev).repeat_interleave(pairs_per_graph)
+    Q = G * pairs_per_graph
+    n = batch.node_counts().to(torch.int64)[graph_index]
+    r = torch.randint(0, 2 ** 31 - 1, (Q, 2), generator=gen, device=dev)
+    u = r[:, 0] % n.clamp(min=1)
+    v = r[:, 1] % (n - 1).clamp(min=1)
+    v = v + (v >= u).to(torch.int64)
+    none = n < 2
+    queries = torch.stack([torch.where(none, -1, u), torch.where(none, -1, v)], 1).to(torch.int32)
+    query_ptr = torch.arange(G + 1, device=dev, dtype=torch.int64) * pairs_per_graph
+    dist = ops.graph_tasks(batch, queries, None if pairs_per_graph == 1 else query_ptr, has_cycle=False, num_components=False).dist
+    return dict(queries=queries, graph_index=graph_index, query_ptr=query_ptr, dist=dist, labels=dist - 1, keep=dist > 0)
+
+
 # ------------------------------------------------------------------------------------------------
 class _Bag:
     """Attribute bag standing in for torch_geometric.data.Data."""

@@ -663,6 +663,24 @@ def _(node_ptr, edge_ptr, rowptr, col, nattr, eattr, max_nodes, max_edges, old_o
             e(E if eattr is not None else 0, torch.uint8), e(8, torch.int32), e(G, torch.int32))
 
 
+@torch.library.custom_op("gtok::graph_tasks", mutates_args=(), device_types="cuda")
+def graph_tasks(node_ptr: Tensor, edge_ptr: Tensor, rowptr: Tensor, col: Tensor, max_nodes: int, max_edges: int, flags: int,
+                queries: Optional[Tensor], query_ptr: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """gtok_graph_tasks: (has_cycle int32 [G], num_components int32 [G], dist int32 [Q] (empty without queries), info int32 [4]) of the
+    batch (include/gtok.h).  flags: GTOK_CSR_SIMPLE_SYMMETRIC where the caller has established it (needed beyond 512 nodes only).
+    queries int32 [Q, 2], query_ptr int64 [G + 1] or None (one query per graph).  Nothing is read back."""
+    b = GraphBatch(int(node_ptr.numel()) - 1, max_nodes, max_edges, node_ptr, edge_ptr, rowptr, col, None, None, None, int(flags))
+    cyc, comp, dist, info = _ops._graph_tasks_launch(b, queries, query_ptr)
+    return cyc, comp, (torch.empty(0, dtype=torch.int32, device=col.device) if dist is None else dist), info
+
+
+@graph_tasks.register_fake
+def _(node_ptr, edge_ptr, rowptr, col, max_nodes, max_edges, flags, queries, query_ptr):
+    G = node_ptr.shape[0] - 1
+    e = lambda n: col.new_empty((n,), dtype=torch.int32)
+    return e(G), e(G), e(queries.shape[0] if queries is not None else 0), e(4)
+
+
 # ---- packed (ragged) rows: include/gtok.h, "packed rows" -----------------------------------------------------------------
 @torch.library.custom_op("gtok::row_offsets", mutates_args=(), device_types="cuda")
 def row_offsets(lens: Tensor, ld: int, align: int) -> Tensor:

@@ -860,6 +860,49 @@ int64_t gtok_csr_relabel_workspace(int32_t num_graphs, int64_t num_entries);
 int gtok_csr_relabel(const gtok_csr *g, const int32_t *target_node_ptr, int32_t target_max_nodes, const int32_t *old_of_new,
                      const gtok_csr_built *out, int32_t *status, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- the task answers of a batch: cycle check and shortest-path distances ----------------------------------------------------
+ * The graph-token corpora are built for two tasks (graph_data_loader/data_loader.py:57-110: `has_cycle ... <p> yes|no` and
+ * `shortest_distance u v ... <p> lenK|INF`; :90-91 also accepts `connected` / `reachable` answer words;
+ * configs/agtt_graph_token.yaml and configs/ibtt_graph_token.yaml train on exactly these).  gtok_graph_tasks answers both for every
+ * graph of a batched CSR - a parsed corpus, a device-built one, a decoded batch - without leaving the device.
+ * Definitions.  The graph of a CSR slice is the SIMPLE UNDIRECTED CLOSURE of its listed entries: nodes 0..N-1, {u,v} an edge iff
+ * (u,v) or (v,u) is listed, u != v; duplicates collapse; self loops are counted apart (`loops`).  One-direction lists, both-direction
+ * lists, duplicates and loops are all legal input (on the paths up to 512 nodes).
+ *   num_components[g]  connected components of the closure, isolated nodes included; 0 for N = 0
+ *   has_cycle[g]       1 iff loops > 0 || m > N - num_components, m = distinct undirected non-loop edges (the graph is no forest:
+ *                      what test/data_distribution_test.py:136-140 asks networkx), else 0
+ *   dist[q]            for the query (u, v) of graph g: the hop count of a shortest path in the closure; 0 when u == v; -1 when
+ *                      unreachable; -2 when an endpoint is outside [0, N_g) - that also raises bit 0 of info[0], and nothing is read
+ *                      through such an endpoint
+ * The reference's label conventions are host arithmetic on top (lenK <-> label K - 1, INF = the item is dropped).
+ * query_nodes int32 [Q, 2] local ids, or NULL (no distances: then query_ptr must be NULL and num_queries 0).  query_ptr int64 [G + 1]:
+ * the queries of graph g are query_ptr[g] .. query_ptr[g + 1]; NULL = exactly one per graph (Q == G), the form gtok_sent's `query`
+ * has.  Consecutive queries of one graph with the same source share one search.  has_cycle / num_components int32 [G] or NULL each;
+ * dist int32 [Q], required iff query_nodes is given.  A call that asks for nothing is a no-op.
+ * info int32 [4], zeroed by the CALLER (several calls may accumulate into one): [0] status bits - 1: a query endpoint outside its
+ * graph, 2: damaged arrays (a slice outside the totals of its pointer array or beyond max_nodes / max_edges: the graph counts as
+ * empty; a row pointer outside [0, E_g] or decreasing: the row counts as empty; a column outside [0, N_g): the entry is skipped;
+ * query_ptr outside [0, Q] or decreasing: the graph's queries are not answered) - nothing is read or written through an index that
+ * was not range-checked, given that the arrays are as long as their pointer arrays say; [1] the largest dist; [2] queries answered
+ * -1; [3] graphs with a cycle (counted when has_cycle or num_components is asked for).
+ * One wave per graph; the search is chosen for the whole batch by g->max_nodes:
+ *   <= 64 nodes    lane v holds closure row v in a 64-bit register (built through 512 bytes of LDS); the closure is symmetric, so
+ *                  the search PULLS: next = ballot((row & frontier) != 0) & ~visited - one ballot per level, no atomics, no queue
+ *   <= 512 nodes   the same over an immutable bit matrix in LDS, W = 2, 4 or 8 words per node (at most 32 KB per wave), lane l
+ *                  owning nodes l + 64 j; frontier and visited are W scalar words, W ballots per level
+ *   <= GTOK_SENT_LARGE_MAX_NODES   GTOK_CSR_SIMPLE_SYMMETRIC batches only (m = E / 2, loops = 0 follow from the flag): a push search
+ *                  over the CSR with a visited bit set, a 16-bit distance table and a 16-bit FIFO in LDS (66 KB per wave at 16,384
+ *                  nodes: one wave per workgroup); 64 nodes are popped per step, never across a level boundary; rows of more than
+ *                  64 entries are read by the whole wave
+ * GTOK_TASKS_KERNEL=reg|lds|csr forces a search (tests); one that cannot hold the batch is GTOK_E_UNSUPPORTED.
+ * Errors, all before any device is asked for: GTOK_E_INVAL for null pointers / negative sizes / a reordered batch / query_nodes
+ * and dist not both given or both NULL / query_ptr == NULL with num_queries != G / queries with no graphs; GTOK_E_TOO_LARGE for
+ * max_nodes beyond GTOK_SENT_LARGE_MAX_NODES; GTOK_E_UNSUPPORTED for more than 512 nodes without GTOK_CSR_SIMPLE_SYMMETRIC.  The
+ * call only enqueues one launch on `stream` (whose device is used): no allocation, no host read-back, no library-owned counters -
+ * it can be captured into a hipGraph.  (Added without an ABI version step, like the decoders: no struct changes.)              */
+int gtok_graph_tasks(const gtok_csr *g, const int32_t *query_nodes, const int64_t *query_ptr, int64_t num_queries, int32_t *has_cycle,
+                     int32_t *num_components, int32_t *dist, int32_t *info, void *stream);
+
 /* Which SENT kernel gtok_sent() will run for this batch ("sent_lane_kernel": lane per graph over the CSR, needs
  * GTOK_CSR_SIMPLE_SYMMETRIC, <= 64 nodes and a large batch; "sent_blane_kernel<W=..>": lane per graph over the
  * adjacency bit-matrix mirror, unlabelled, <= 256 nodes; "sent_reg_kernel": wave per graph, <= 64 nodes;
