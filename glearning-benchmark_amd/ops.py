@@ -1323,6 +1323,306 @@ def check_task_labels(batch: GraphBatch, task: str, labels: torch.Tensor, query_
     return has & asked & ((r.dist - 1) != labels)
 
 
+# ------------------------------------------------------------------------------------------------
+# a key per graph, duplicate graphs, split leakage (include/gtok.h: gtok_graph_keys)
+# ------------------------------------------------------------------------------------------------
+KEYS_MAX_NODES_ANY = 512       # beyond it closure keys stream the CSR itself and need GTOK_CSR_SIMPLE_SYMMETRIC
+KEYS_DAMAGED = 2               # info[0] bit
+_KEY_MODES = {"listed": _lib.KEYS_LISTED, "closure": _lib.KEYS_CLOSURE}
+
+
+def _keys_flags(batches, mode: str, attrs: bool) -> int:
+    """GTOK_KEYS_* of (mode, attrs); the argument errors that need no device"""
+    if mode not in _KEY_MODES:
+        raise ValueError('graph_keys: mode must be "listed" or "closure"')
+    if attrs and mode == "closure":
+        raise ValueError("graph_keys: closure keys are structure only - attrs=True goes with mode=\"listed\" (GTOK_E_INVAL)")
+    for b in batches:
+        if attrs and (b.nattr is None or b.eattr is None):
+            raise ValueError("graph_keys: attrs=True needs a batch with node and edge attributes (GTOK_E_INVAL)")
+        if b.graph_ids is not None:
+            raise ValueError("graph_keys: a batch in dataset order only (not ops.lane_sorted's copy)")
+    return _KEY_MODES[mode] | (_lib.KEYS_ATTRS if attrs else 0)
+
+
+def _labels_of(batch: GraphBatch, labels, dev) -> Optional[torch.Tensor]:
+    if labels is None:
+        return None
+    labels = torch.as_tensor(labels).to(dev, dtype=torch.int32).contiguous().reshape(-1)
+    if int(labels.numel()) != batch.num_graphs:
+        raise ValueError("graph_keys: one label per graph")
+    return labels
+
+
+def _graph_keys_launch(batch: GraphBatch, labels: Optional[torch.Tensor], flags: int, info: Optional[torch.Tensor] = None):
+    """gtok_graph_keys on the current stream -> (keys int64 [G, 2], info int32 [4]); no host read."""
+    _need_gpu(batch.col, "graph_keys")
+    _need(_lib.GRAPH_KEYS_SYMBOLS, "gtok_graph_keys")
+    dev, G = batch.device, batch.num_graphs
+    if batch.max_nodes > _lib.SENT_LARGE_MAX_NODES:
+        raise _lib.GtokError(f"graph_keys: a graph of {batch.max_nodes} nodes is beyond the {_lib.SENT_LARGE_MAX_NODES} whose ids fit a key's "
+                             "14-bit fields (GTOK_E_TOO_LARGE)")
+    if (flags & _lib.KEYS_CLOSURE) and batch.max_nodes > KEYS_MAX_NODES_ANY and not (batch.flags & _lib.CSR_SIMPLE_SYMMETRIC):
+        raise _lib.GtokError(f"graph_keys: closure keys of graphs of more than {KEYS_MAX_NODES_ANY} nodes (this batch: {batch.max_nodes}) are read "
+                             "off the CSR itself, which must list every edge once in each direction, without loops: the batch does not "
+                             "carry GTOK_CSR_SIMPLE_SYMMETRIC (GTOK_E_UNSUPPORTED)")
+    labels = _labels_of(batch, labels, dev)
+    if info is None:
+        info = torch.zeros(4, dtype=torch.int32, device=dev)
+    elif info.dtype != torch.int32 or info.numel() != 4 or info.device != dev or not info.is_contiguous():
+        raise ValueError("graph_keys: info must be int32 [4] on the batch's device")
+    keys = torch.empty((G, 2), dtype=torch.int64, device=dev)
+    if G == 0:
+        return keys, info
+    cs = batch.c_struct()
+    check(lib().gtok_graph_keys(ctypes.byref(cs), None if labels is None else labels.data_ptr(), flags, keys.data_ptr(), info.data_ptr(),
+                                _stream(dev)), "gtok_graph_keys")
+    return keys, info
+
+
+def graph_keys(batch: GraphBatch, labels: Optional[torch.Tensor] = None, mode: str = "listed", attrs: bool = False,
+               info: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gtok_graph_keys: a 128-bit key per graph -> int64 [G, 2] on the device (the two uint64 words, bit for bit).  mode "listed": the
+    reference's key (test/train_performance_test.py:70-74) - all listed entries with their endpoints sorted, duplicates and loops
+    counting, N and the label; attrs=True adds the edge and node attribute bytes (ZINC).  mode "closure": the key of the simple
+    undirected closure - a once-listed, a both-directions and a messy listing of one graph share it (beyond 512 nodes: a
+    GTOK_CSR_SIMPLE_SYMMETRIC batch).  A key identifies a NUMBERED graph, not an isomorphism class, and equal keys only make equal
+    graphs overwhelmingly likely: ops.duplicate_graphs(confirm=True) compares.  labels int32 [G] or None; info: an int32 [4] tensor of
+    the caller's to accumulate the status into (bit KEYS_DAMAGED, the damaged graphs), else it is dropped."""
+    flags = _keys_flags([batch], mode, attrs)
+    return _graph_keys_launch(batch, labels, flags, info)[0]
+
+
+class Duplicates:
+    """What ops.duplicate_graphs returns - device tensors over the concatenation of the splits: group int64 [T] (the index of the first
+    graph of graph i's class), split int64 [T], is_first bool [T]; split_ptr: the splits' offsets (host ints)."""
+    __slots__ = ("group", "split", "is_first", "split_ptr")
+
+    def __init__(self, group, split, is_first, split_ptr):
+        self.group, self.split, self.is_first, self.split_ptr = group, split, is_first, list(split_ptr)
+
+    @property
+    def num_splits(self) -> int:
+        return len(self.split_ptr) - 1
+
+    def _presence(self):
+        """(bool [classes, S]: the class has a member in the split; int64 [T]: the class of every graph)"""
+        heads, cls = torch.unique(self.group, return_inverse=True)
+        P = torch.zeros((int(heads.numel()), self.num_splits), dtype=torch.bool, device=self.group.device)
+        P[cls, self.split] = True
+        return P, cls
+
+    def unique_per_split(self) -> torch.Tensor:
+        """int64 [S]: the distinct graphs of every split (the reference's len(hashes[split]))"""
+        return self._presence()[0].sum(0)
+
+    def overlap(self) -> torch.Tensor:
+        """int64 [S, S]: the classes present in both splits (the reference's len(hashes[a] & hashes[b])); the diagonal = unique_per_split"""
+        P, _ = self._presence()
+        if self.num_splits == 0:
+            return torch.zeros((0, 0), dtype=torch.int64, device=P.device)
+        return torch.stack([(P & P[:, a:a + 1]).sum(0) for a in range(self.num_splits)])
+
+    def leaked(self, a: int, b: int) -> torch.Tensor:
+        """int64: the graphs of split b (indices inside split b) whose class occurs in split a"""
+        P, cls = self._presence()
+        hit = (self.split == b) & P[cls, a]
+        return hit.nonzero().reshape(-1) - self.split_ptr[b]
+
+
+def _group_by_keys(keys: torch.Tensor) -> torch.Tensor:
+    """group[i] = the lowest index with graph i's key: two stable sorts of the key columns, then head flags"""
+    T = int(keys.shape[0])
+    ar = torch.arange(T, device=keys.device)
+    if T == 0:
+        return ar
+    o1 = torch.sort(keys[:, 1], stable=True).indices
+    order = o1[torch.sort(keys[o1, 0], stable=True).indices]
+    ks = keys[order]
+    head = torch.ones(T, dtype=torch.bool, device=keys.device)
+    head[1:] = (ks[1:] != ks[:-1]).any(1)
+    head_pos = torch.cummax(torch.where(head, ar, torch.zeros_like(ar)), 0).values
+    group = torch.empty_like(ar)
+    group[order] = order[head_pos]
+    return group
+
+
+def _canonical_lists(bl, ptr, gs: torch.Tensor, closure: bool, attrs: bool):
+    """The canonical folded entry lists of the graphs `gs` (sorted indices into the concatenation): (graph slot, a, b, t) packed into
+    int64, sorted (closure: distinct) -> (vals = the packed (a, b, t), starts, counts per slot); with attrs also the node bytes the same
+    way.  Torch gathers over the chosen graphs only."""
+    dev = gs.device
+    K = int(gs.numel())
+    packed, nvals = [], []
+    for s, b in enumerate(bl):
+        sel = ((gs >= ptr[s]) & (gs < ptr[s + 1])).nonzero().reshape(-1)
+        if sel.numel() == 0:
+            continue
+        l = gs[sel] - ptr[s]
+        nptr, eptr = b.node_ptr.to(torch.int64), b.edge_ptr
+        nc = nptr[l + 1] - nptr[l]
+        jn = torch.repeat_interleave(torch.arange(int(l.numel()), device=dev), nc)
+        node_loc = torch.arange(int(jn.numel()), device=dev) - (torch.cumsum(nc, 0) - nc)[jn]
+        rowidx = nptr[l][jn] + l[jn] + node_loc
+        x = b.rowptr[rowidx].to(torch.int64)
+        deg = (b.rowptr[rowidx + 1].to(torch.int64) - x).clamp(min=0)
+        je = torch.repeat_interleave(torch.arange(int(jn.numel()), device=dev), deg)
+        k = torch.arange(int(je.numel()), device=dev) - (torch.cumsum(deg, 0) - deg)[je]
+        ent = eptr[l][jn][je] + x[je] + k
+        u, c = node_loc[je], b.col[ent].to(torch.int64)
+        t = b.eattr[ent].to(torch.int64) if attrs else torch.zeros_like(u)
+        slot = sel[jn][je]
+        packed.append((((slot << 14 | torch.minimum(u, c)) << 14 | torch.maximum(u, c)) << 8) | t)
+        if attrs:
+            nvals.append(b.nattr[nptr[l][jn] + node_loc].to(torch.int64))
+    vals = torch.sort(torch.cat(packed)).values if packed else torch.zeros(0, dtype=torch.int64, device=dev)
+    if closure:
+        vals = torch.unique_consecutive(vals)
+    cnt = torch.bincount(vals >> 36, minlength=K)
+    out = [(vals & ((1 << 36) - 1), torch.cumsum(cnt, 0) - cnt, cnt)]
+    if attrs:
+        nv = torch.cat(nvals) if nvals else torch.zeros(0, dtype=torch.int64, device=dev)
+        n_all = torch.cat([b.node_counts().to(torch.int64) for b in bl])[gs]
+        out.append((nv, torch.cumsum(n_all, 0) - n_all, n_all))
+    return out
+
+
+def _segments_equal(vals, starts, cnts, sa, sb) -> torch.Tensor:
+    """bool [P]: the lists of slots sa[p] and sb[p] are equal"""
+    same = cnts[sa] == cnts[sb]
+    c = torch.where(same, cnts[sa], torch.zeros_like(cnts[sa]))
+    P = int(sa.numel())
+    pid = torch.repeat_interleave(torch.arange(P, device=sa.device), c)
+    off = torch.arange(int(pid.numel()), device=sa.device) - (torch.cumsum(c, 0) - c)[pid]
+    diff = (vals[starts[sa][pid] + off] != vals[starts[sb][pid] + off]).to(torch.int64)
+    bad = torch.zeros(P, dtype=torch.int64, device=sa.device).index_add_(0, pid, diff)
+    return same & (bad == 0)
+
+
+def _confirm_groups(bl, ll, ptr, group: torch.Tensor, closure: bool, attrs: bool, budget_bytes: int) -> torch.Tensor:
+    """Classes by key -> classes by the graphs themselves: every member of a class of two or more is compared with the class's first
+    member - N, the label, the canonical entry list (and the node bytes) - in chunks of at most ~budget_bytes of gathered lists; the
+    members that differ (a digest collision, or keys= that say nothing) leave the class, the first of them heads a new one and the
+    others are compared with it in the next round."""
+    dev, T = group.device, int(group.numel())
+    ar = torch.arange(T, device=dev)
+    n_all = torch.cat([b.node_counts().to(torch.int64) for b in bl])
+    e_all = torch.cat([b.edge_ptr[1:] - b.edge_ptr[:-1] for b in bl])
+    lab = torch.cat([torch.zeros(b.num_graphs, dtype=torch.int32, device=dev) if l is None else l for b, l in zip(bl, ll)])
+    per_chunk = max(1, int(budget_bytes) // 64)              # ~8 int64 temporaries per gathered entry
+    group = group.clone()
+    pending = group != ar
+    while True:
+        mem = pending.nonzero().reshape(-1)
+        if mem.numel() == 0:
+            break
+        heads = group[mem]
+        ok = (n_all[mem] == n_all[heads]) & (lab[mem] == lab[heads])
+        if not closure:
+            ok &= e_all[mem] == e_all[heads]
+        cost = e_all[mem] + e_all[heads] + (n_all[mem] + n_all[heads] if attrs else 0) + 1
+        chunk = (torch.cumsum(cost, 0) - cost) // per_chunk
+        sizes = torch.unique_consecutive(chunk, return_counts=True)[1].tolist()
+        i0 = 0
+        for sz in sizes:
+            m, h = mem[i0:i0 + sz], heads[i0:i0 + sz]
+            gs, inv = torch.unique(torch.cat([m, h]), return_inverse=True)
+            eq = torch.ones(sz, dtype=torch.bool, device=dev)
+            for vals, starts, cnts in _canonical_lists(bl, ptr, gs, closure, attrs):
+                eq &= _segments_equal(vals, starts, cnts, inv[:sz], inv[sz:])
+            ok[i0:i0 + sz] &= eq
+            i0 += sz
+        pending[mem[ok]] = False
+        bad = mem[~ok]
+        if bad.numel() == 0:
+            break
+        first_bad = torch.full((T,), T, dtype=torch.int64, device=dev).scatter_reduce_(0, group[bad], bad, "amin")
+        group[bad] = first_bad[group[bad]]
+        pending[bad] = group[bad] != bad
+    return group
+
+
+def duplicate_graphs(batches, labels=None, mode: str = "listed", attrs: bool = False, confirm: bool = True, keys=None,
+                     budget_bytes: int = 256 << 20) -> Duplicates:
+    """The classes of equal graphs of one batch or of a sequence of batches (the splits of a corpus), on the device -> Duplicates over
+    their concatenation.  Two graphs are equal when the reference's key says so (ops.graph_keys: mode, attrs; labels: one tensor per
+    batch, or None).  Keys come from gtok_graph_keys unless `keys` supplies them (int64 [T, 2], or one [G, 2] per batch); grouping is
+    two stable sorts of the key columns.  confirm=True makes the answer exact, as the reference's set of tuples is: the members of
+    every class of two or more are compared with the class's first member, and one that differs is re-grouped by the graphs
+    themselves, never merged.  confirm=False trusts the 128 bits."""
+    single = isinstance(batches, GraphBatch)
+    bl = [batches] if single else list(batches)
+    if not bl:
+        raise ValueError("duplicate_graphs: no batch")
+    if labels is None:
+        ll = [None] * len(bl)
+    else:
+        ll = [labels] if single else list(labels)
+        if len(ll) != len(bl):
+            raise ValueError("duplicate_graphs: one label tensor (or None) per batch")
+    flags = _keys_flags(bl, mode, attrs)
+    dev = bl[0].device
+    if any(b.device != dev for b in bl):
+        raise ValueError("duplicate_graphs: batches on different devices")
+    ll = [_labels_of(b, l, dev) for b, l in zip(bl, ll)]
+    ptr = [0]
+    for b in bl:
+        ptr.append(ptr[-1] + b.num_graphs)
+    T = ptr[-1]
+    if keys is None:
+        keys = torch.cat([_graph_keys_launch(b, l, flags)[0] for b, l in zip(bl, ll)])
+    else:
+        keys = torch.cat([torch.as_tensor(k).reshape(-1, 2) for k in keys]) if isinstance(keys, (list, tuple)) else torch.as_tensor(keys)
+        keys = keys.to(dev, dtype=torch.int64)
+        if tuple(keys.shape) != (T, 2):
+            raise ValueError(f"duplicate_graphs: keys must be int64 [{T}, 2]")
+    split = torch.repeat_interleave(torch.arange(len(bl), device=dev), torch.tensor([b.num_graphs for b in bl], device=dev))
+    group = _group_by_keys(keys)
+    if confirm and T:
+        group = _confirm_groups(bl, ll, ptr, group, mode == "closure", attrs, budget_bytes)
+    return Duplicates(group, split, group == torch.arange(T, device=dev), ptr)
+
+
+def split_leakage(splits: Dict[str, object], mode: str = "listed", attrs: bool = False, confirm: bool = True) -> Dict[str, object]:
+    """The reference's data-leakage report (test/train_performance_test.py:146-207, Test 2) for {"train": (batch, labels), ...} (a
+    value may also be a batch alone), computed on the device with one small read-back:
+      total / unique   {split: graphs, distinct graphs}           (`{split}: {unique} unique graphs (from {total} total)`)
+      overlap          {(a, b): classes present in both}          for every pair a before b (train-val, train-test, val-test)
+      example          {(a, b): (index in a, index in b) of one shared graph, or None}
+      leakage          any overlap at all
+      duplicates       the Duplicates object (device tensors)"""
+    names = list(splits)
+    vals = [v if isinstance(v, (tuple, list)) else (v, None) for v in splits.values()]
+    dup = duplicate_graphs([v[0] for v in vals], [v[1] for v in vals], mode, attrs, confirm)
+    S, T, dev = len(names), dup.split_ptr[-1], dup.group.device
+    P, cls = dup._presence()
+    ov = dup.overlap()
+    ar = torch.arange(T, device=dev)
+    pairs = [(a, b) for a in range(S) for b in range(a + 1, S)]
+    ex = []
+    for a, b in pairs:
+        if T == 0:
+            ex += [ar.new_tensor(0), ar.new_tensor(0)]
+            continue
+        in_b = (dup.split == b) & P[cls, a]
+        ib = torch.where(in_b, ar, torch.full_like(ar, T)).min()
+        g = dup.group[ib.clamp(max=T - 1)]
+        ia = torch.where((dup.split == a) & (dup.group == g) & (ib < T), ar, torch.full_like(ar, T)).min()
+        ex += [ia, ib]
+    flat = torch.cat([ov.reshape(-1)] + [torch.stack(ex)] * bool(ex)).tolist()          # the one read-back
+    ovh = [flat[a * S:(a + 1) * S] for a in range(S)]
+    exh = flat[S * S:]
+    out = dict(splits=names, total={n: dup.split_ptr[i + 1] - dup.split_ptr[i] for i, n in enumerate(names)},
+               unique={n: ovh[i][i] for i, n in enumerate(names)}, overlap={}, example={}, duplicates=dup)
+    for p, (a, b) in enumerate(pairs):
+        key = (names[a], names[b])
+        out["overlap"][key] = ovh[a][b]
+        ia, ib = exh[2 * p], exh[2 * p + 1]
+        out["example"][key] = (ia - dup.split_ptr[a], ib - dup.split_ptr[b]) if ovh[a][b] else None
+    out["leakage"] = any(out["overlap"].values())
+    return out
+
+
 def remap_zinc(ids: torch.Tensor, ln: torch.Tensor, idx_offset: int, node_idx_offset: int,
                edge_idx_offset: int) -> torch.Tensor:
     _need_gpu(ids, "remap_zinc")

@@ -681,6 +681,23 @@ def _(node_ptr, edge_ptr, rowptr, col, max_nodes, max_edges, flags, queries, que
     return e(G), e(G), e(queries.shape[0] if queries is not None else 0), e(4)
 
 
+@torch.library.custom_op("gtok::graph_keys", mutates_args=(), device_types="cuda")
+def graph_keys(node_ptr: Tensor, edge_ptr: Tensor, rowptr: Tensor, col: Tensor, nattr: Optional[Tensor], eattr: Optional[Tensor],
+               max_nodes: int, max_edges: int, flags: int, labels: Optional[Tensor], mode: int, attrs: bool) -> Tensor:
+    """gtok_graph_keys: int64 [G, 2], the 128-bit key of every graph of the batch (include/gtok.h).  flags: GTOK_CSR_SIMPLE_SYMMETRIC
+    where the caller has established it (closure keys beyond 512 nodes need it).  mode: 0 = GTOK_KEYS_LISTED, 1 = GTOK_KEYS_CLOSURE;
+    attrs: the attribute bytes count (listed keys only; needs nattr and eattr).  labels int32 [G] or None.  Nothing is read back."""
+    if mode not in (_lib.KEYS_LISTED, _lib.KEYS_CLOSURE):
+        raise ValueError("gtok::graph_keys: mode must be 0 (listed) or 1 (closure)")
+    b = GraphBatch(int(node_ptr.numel()) - 1, max_nodes, max_edges, node_ptr, edge_ptr, rowptr, col, None, nattr, eattr, int(flags))
+    return _ops.graph_keys(b, labels, "closure" if mode == _lib.KEYS_CLOSURE else "listed", bool(attrs))
+
+
+@graph_keys.register_fake
+def _(node_ptr, edge_ptr, rowptr, col, nattr, eattr, max_nodes, max_edges, flags, labels, mode, attrs):
+    return col.new_empty((node_ptr.shape[0] - 1, 2), dtype=torch.int64)
+
+
 # ---- packed (ragged) rows: include/gtok.h, "packed rows" -----------------------------------------------------------------
 @torch.library.custom_op("gtok::row_offsets", mutates_args=(), device_types="cuda")
 def row_offsets(lens: Tensor, ld: int, align: int) -> Tensor:

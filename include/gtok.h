@@ -903,6 +903,48 @@ int gtok_csr_relabel(const gtok_csr *g, const int32_t *target_node_ptr, int32_t 
 int gtok_graph_tasks(const gtok_csr *g, const int32_t *query_nodes, const int64_t *query_ptr, int64_t num_queries, int32_t *has_cycle,
                      int32_t *num_components, int32_t *dist, int32_t *info, void *stream);
 
+/* ---- a key per graph: duplicate graphs and split leakage ------------------------------------------------------------------------
+ * The reference checks a corpus for leaked test graphs (test/train_performance_test.py:70-74 compute_graph_hash, :146-207
+ * test_data_leakage): every graph gets the key (num_nodes, the sorted list of its listed edges with each edge's endpoints sorted,
+ * label), and the splits' key sets are intersected.  gtok_graph_keys gives every graph of a batched CSR a 128-bit digest of exactly
+ * that key in one pass over the CSR, keys[2 g], keys[2 g + 1]; grouping equal keys (and confirming them exactly) is torch plumbing
+ * on top (ops.duplicate_graphs, ops.split_leakage).  The digest is a keyed multiset sum - it does not depend on the order of the
+ * entries or on their orientation; its arithmetic is csrc/gtok_graph_keys_hash.hpp, frozen in DESIGN.md.
+ * A key identifies a NUMBERED graph, as the reference's tuple does: isomorphic graphs numbered differently get different keys.  It
+ * is no isomorphism class and no canonical form.  Equal keys of different graphs are possible in principle (128 bits).
+ * flags = a mode, optionally | GTOK_KEYS_ATTRS:
+ *   GTOK_KEYS_LISTED   the reference's key.  The terms are ALL listed entries, folded to a <= b: duplicates count, self loops count -
+ *                      a graph listed once and the same graph listed in both directions get different keys, as there.  With
+ *                      GTOK_KEYS_ATTRS every entry carries its eattr byte and every node adds a term with its nattr byte (ZINC;
+ *                      needs g->nattr and g->eattr).
+ *   GTOK_KEYS_CLOSURE  the key of the graph as gtok_graph_tasks defines it: the simple undirected closure of the entries - every
+ *                      distinct edge {u, v}, u != v, counts once and every node with a self loop counts once.  By definition it
+ *                      equals the LISTED key of that graph listed once and simple (each edge once in either orientation, each looped
+ *                      node's loop once): a once-listed, a both-directions and a messy listing of one graph share it.  Structure
+ *                      only: with GTOK_KEYS_ATTRS it is GTOK_E_INVAL.
+ * labels int32 [G] or NULL (label 0 for every graph).  keys uint64 [G, 2].  info int32 [4], zeroed by the CALLER: [0] status bits -
+ * 2: damaged arrays (a slice outside the totals of its pointer array or beyond max_nodes / max_edges: the graph counts as empty; a
+ * row pointer outside [0, E_g] or decreasing: the row is skipped; a column outside [0, N_g): the entry is skipped) - nothing is read
+ * through an index that was not range-checked; [1] the graphs with such damage; [2], [3] are not written.  Nothing is written outside
+ * keys[2 g .. 2 g + 1] and info.
+ * One wave per graph (independent waves, gtok_graph_tasks' conventions):
+ *   LISTED   any batch up to GTOK_SENT_LARGE_MAX_NODES nodes: a stream over rowptr / col (/ eattr / nattr) with coalesced reads - the
+ *            bounds of 64 rows, then their entries 64 consecutive ones per step, each lane finding its entry's row among the 64 row
+ *            starts; a row of more than 64 entries is thereby read by the whole wave
+ *   CLOSURE  chosen for the whole batch by g->max_nodes: <= 64 nodes closure rows in registers; <= 512 nodes the bit matrix in LDS,
+ *            each lane enumerating the set bits b > v of the rows it owns (the diagonal kept apart for loops); beyond 512 nodes
+ *            GTOK_CSR_SIMPLE_SYMMETRIC batches only - the listed stream keeping the entries with u < v - GTOK_E_UNSUPPORTED without the
+ *            flag.  GTOK_KEYS_KERNEL=reg|lds|csr forces one (tests); one that cannot hold the batch is GTOK_E_UNSUPPORTED.
+ * Errors, all before any device is asked for: GTOK_E_INVAL for null pointers / negative sizes / a reordered batch / unknown flag bits /
+ * GTOK_KEYS_ATTRS with GTOK_KEYS_CLOSURE or without the attribute arrays; GTOK_E_TOO_LARGE for max_nodes beyond
+ * GTOK_SENT_LARGE_MAX_NODES; num_graphs == 0 is a no-op.  The call only enqueues one launch on `stream` (whose device is used): no
+ * allocation, no host read-back, no library-owned counters - it can be captured into a hipGraph.  (Added without an ABI version step:
+ * no struct changes.)                                                                                                          */
+#define GTOK_KEYS_LISTED 0
+#define GTOK_KEYS_CLOSURE 1
+#define GTOK_KEYS_ATTRS 2
+int gtok_graph_keys(const gtok_csr *g, const int32_t *labels, int32_t flags, uint64_t *keys, int32_t *info, void *stream);
+
 /* Which SENT kernel gtok_sent() will run for this batch ("sent_lane_kernel": lane per graph over the CSR, needs
  * GTOK_CSR_SIMPLE_SYMMETRIC, <= 64 nodes and a large batch; "sent_blane_kernel<W=..>": lane per graph over the
  * adjacency bit-matrix mirror, unlabelled, <= 256 nodes; "sent_reg_kernel": wave per graph, <= 64 nodes;
