@@ -95,6 +95,12 @@ class GtokSentParams(ctypes.Structure):
     ]
 
 
+class GtokSentConsts(ctypes.Structure):
+    """include/gtok.h: gtok_sent_consts - the constants mirror gtok_sent_prepared reads."""
+    _fields_ = [("ntok8", ctypes.c_void_p), ("etok8", ctypes.c_void_p), ("max_num_nodes", ctypes.c_int32),
+                ("num_node_types", ctypes.c_int32), ("num_edge_types", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 # every symbol include/gtok.h declares: (restype, argtypes)
 _I, _P = ctypes.c_int32, ctypes.c_void_p
 SYMBOLS = {
@@ -102,6 +108,8 @@ SYMBOLS = {
     "gtok_ibtt_synth": (_I, [ctypes.POINTER(GtokCsr), _P, _I, _P, _I, _I, _P, _I, _P, _P]),
     "gtok_text_to_ids": (_I, [_P, _P, _I, ctypes.POINTER(GtokVocabTable), _I, _I, _P, _I, _P, _P]),
     "gtok_sent": (_I, [ctypes.POINTER(GtokCsr), ctypes.POINTER(GtokSentParams), _P, _I, _P, _P]),
+    "gtok_sent_lane_consts": (_I, [ctypes.POINTER(GtokCsr), ctypes.POINTER(GtokSentParams), ctypes.c_int64, ctypes.c_int64, _P, _P, _P, _P]),
+    "gtok_sent_prepared": (_I, [ctypes.POINTER(GtokCsr), ctypes.POINTER(GtokSentParams), ctypes.POINTER(GtokSentConsts), _P, _I, _P, _P]),
     "gtok_sent_large_workspace": (ctypes.c_int64, [_I, _I, ctypes.c_int64]),
     "gtok_sent_large": (_I, [ctypes.POINTER(GtokCsr), ctypes.POINTER(GtokSentParams), _P, _I, _P, _P, ctypes.c_int64, _P]),
     "gtok_sent_packed": (_I, [ctypes.POINTER(GtokCsr), ctypes.POINTER(GtokSentParams), _P, _I, _P, _P, ctypes.c_int64, _P, _P, _P]),
@@ -162,8 +170,9 @@ ORDER_SYMBOLS = ("gtok_sent_large_order", "gtok_csr_relabel_workspace", "gtok_cs
 ZINC_DECODE_SYMBOLS = ("gtok_unremap_zinc", "gtok_sent_decode_zinc_sizes", "gtok_sent_decode_zinc_csr")   # likewise (ops.sent_decode_zinc_csr)
 GRAPH_TASKS_SYMBOLS = ("gtok_graph_tasks",)                                 # likewise (ops.graph_tasks)
 GRAPH_KEYS_SYMBOLS = ("gtok_graph_keys",)                                   # likewise (ops.graph_keys)
+LANE_CONSTS_SYMBOLS = ("gtok_sent_lane_consts", "gtok_sent_prepared")       # likewise (ops.lane_consts; ops.sent goes without)
 _MAY_BE_MISSING = frozenset(OPTIONAL_SYMBOLS + DECODE_CSR_SYMBOLS + IBTT_DECODE_SYMBOLS + ORDER_SYMBOLS + ZINC_DECODE_SYMBOLS + GRAPH_TASKS_SYMBOLS
-                            + GRAPH_KEYS_SYMBOLS)
+                            + GRAPH_KEYS_SYMBOLS + LANE_CONSTS_SYMBOLS)
 KEYS_LISTED, KEYS_CLOSURE, KEYS_ATTRS = 0, 1, 2                             # include/gtok.h: GTOK_KEYS_*
 IBTT_GRAMMAR_ZINC, IBTT_GRAMMAR_SYNTH = 0, 1                                # include/gtok.h: GTOK_IBTT_GRAMMAR_*
 

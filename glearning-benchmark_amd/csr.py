@@ -5,7 +5,7 @@ what graph_data_loader/zinc_dataset_autograph.py:51-73 and
 graph_data_loader/graph_token_dataset_autograph.py:338-348 hand to the
 tokenizer), then resident on the device for every epoch.
 """
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Optional, Sequence
 
 import numpy as np
@@ -75,6 +75,7 @@ class GraphBatch:
     adj_unusable: bool = False                   # gtok_csr_adjbits found a closure degree above 255: do not try again
     checked: bool = False                        # flags were established on the device (gtok_csr_check; torch_ops: raw-tensor calls)
     prepared: bool = False                       # the caller built the layouts itself (torch.ops.gtok.csr_prepare): ops.sent prepares nothing
+    lane_consts: dict = field(default_factory=dict)   # a reordered batch's constants mirrors (ops.lane_consts), by tokenizer settings
 
     @property
     def device(self) -> torch.device:

@@ -11,6 +11,8 @@
 //                        block-wise pointer chase, twelve small launches, no host round trip
 //   gtok_csr_from_coo    the batched CSR itself, from PyG collated storage (edge_index with local ids + slices + optional
 //                        indices): what GraphBatch.from_coo does on the host, in four launches, no host round trip
+//   gtok_sent_lane_consts  the token of every node / entry type byte of a reordered batch under the ZINC remap (ntok8 / etok8):
+//                        what sent_lane_kernel would otherwise recompute at every visit of every epoch
 //
 // Everything here is integer bookkeeping over arrays of a few MB: the kernels are bound by launch gaps and by the
 // latency of dependent loads, not by HBM; their job is to cost well under one epoch of tokenization, once.
@@ -19,6 +21,7 @@
 
 #include "gtok.h"
 #include "gtok_common.hpp"
+#include "gtok_sent_reg.hpp"   // remap_node_type_u / remap_edge_type_u: the mirror holds what the walk would emit
 
 namespace gtok {
 
@@ -977,6 +980,47 @@ extern "C" int gtok_csr_lane_sort(const gtok_csr *g, int32_t lds_budget, int32_t
   hipLaunchKernelGGL(unit_chase_kernel, dim3(1), dim3(256), 0, s, table, w.ublocks, G, entry, ubase, o->unit_ptr, o->info);
   hipLaunchKernelGGL(unit_write_kernel, dim3(w.ublocks), dim3(64), 0, s, hop, G, entry, ubase, o->unit_ptr);
   hipLaunchKernelGGL(unit_info_kernel, dim3(ngroups), dim3(256), 0, s, o->unit_ptr, o->node_ptr, o->edge_ptr, o->unit_info, o->info);
+  return hipGetLastError() == hipSuccess ? GTOK_OK : GTOK_E_LAUNCH;
+}
+
+namespace gtok {
+
+// ---------------------------------------------------------------------------------------------------------------
+// constants mirror of the labelled + remapped lane-per-graph walk (include/gtok.h: gtok_sent_lane_consts): a thread per
+// attribute byte, nodes first and entries behind them; nothing is read through an offset.  A token that does not fit a
+// byte sets bit 0 of the status word, once per wave that saw one.
+// ---------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) lane_consts_kernel(const uint8_t *__restrict__ nattr, const uint8_t *__restrict__ eattr, int64_t N, int64_t E,
+                                                          uint32_t node_off, uint32_t ntypes, uint32_t edge_off,
+                                                          uint8_t *__restrict__ ntok8, uint8_t *__restrict__ etok8, int32_t *status) {
+  const int64_t step = (int64_t)gridDim.x * blockDim.x;
+  bool wide = false;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N + E; i += step) {
+    uint32_t t;
+    if (i < N) { t = remap_node_type_u(nattr[i], node_off, ntypes); ntok8[i] = (uint8_t)t; }
+    else { t = remap_edge_type_u(eattr[i - N], edge_off); etok8[i - N] = (uint8_t)t; }
+    wide |= t > 255u;
+  }
+  if (__ballot(wide) != 0 && (threadIdx.x & 63) == 0) atomicOr(status, 1);
+}
+
+}  // namespace gtok
+
+extern "C" int gtok_sent_lane_consts(const gtok_csr *g, const gtok_sent_params *p, int64_t num_nodes, int64_t num_entries, uint8_t *ntok8,
+                                     uint8_t *etok8, int32_t *status, void *stream) {
+  DeviceScope device_scope((hipStream_t)stream);
+  if (!device_scope.ok()) return GTOK_E_NO_DEVICE;
+  if (!g || !p || !status || num_nodes < 0 || num_entries < 0 || g->num_graphs < 0) return GTOK_E_INVAL;
+  if (!g->graph_ids || !g->unit_ptr || !p->labeled || !p->remap_zinc || p->max_num_nodes < 0 || p->num_node_types < 0) return GTOK_E_INVAL;
+  if ((num_nodes && (!g->nattr || !ntok8)) || (num_entries && (!g->eattr || !etok8))) return GTOK_E_INVAL;
+  hipStream_t s = (hipStream_t)stream;
+  if (hipMemsetAsync(status, 0, sizeof(int32_t), s) != hipSuccess) return GTOK_E_LAUNCH;
+  const int64_t total = num_nodes + num_entries;
+  if (total == 0) return GTOK_OK;
+  const uint32_t node_off = (uint32_t)(GTOK_SENT_IDX_OFFSET + p->max_num_nodes), edge_off = node_off + (uint32_t)p->num_node_types;
+  const int64_t nb = (total + 255) / 256;
+  hipLaunchKernelGGL(lane_consts_kernel, dim3((unsigned)(nb > 16384 ? 16384 : nb)), dim3(256), 0, s, g->nattr, g->eattr, num_nodes, num_entries,
+                     node_off, (uint32_t)p->num_node_types, edge_off, ntok8, etok8, status);
   return hipGetLastError() == hipSuccess ? GTOK_OK : GTOK_E_LAUNCH;
 }
 

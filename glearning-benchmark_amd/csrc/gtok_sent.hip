@@ -81,6 +81,7 @@ struct PackDest { void *packed; int64_t capacity; int64_t *row_start; int64_t *s
 struct SentCall {
   const gtok_csr *g; const gtok_sent_params *p; int32_t *out; int32_t ld; int32_t *out_len;
   const PackDest *pd;      // gtok_sent_packed: where the walk packs its rows; else null
+  const gtok_sent_consts *consts;   // gtok_sent_prepared: the constants mirror of the batch; else null
   hipStream_t stream; int dev;   // (the stream's device: DeviceScope)
   SentKernel which;
   int K, maxn, maxe;       // epochs per launch, largest graph (>= 1 each)
@@ -115,6 +116,12 @@ int check_sent_args(SentCall &c) {
   c.maxe = g->max_edges > 0 ? g->max_edges : 1;
   const SentKernel which = c.which = choose_sent_kernel(g, p);
   if (which == SentKernel::None) return GTOK_E_INVAL;       // a reordered batch the lane-per-graph kernel cannot take
+  if (const gtok_sent_consts *k = c.consts) {
+    // the constants mirror: tokens of THIS reordered batch's type bytes under THESE settings, for the instantiation that stages bytes
+    if (which != SentKernel::Lane || !g->graph_ids || !g->unit_ptr || !g->rowptr8 || !g->col8 || !p->labeled || !p->remap_zinc) return GTOK_E_INVAL;
+    if (!k->ntok8 || !k->etok8 || k->reserved != 0) return GTOK_E_INVAL;
+    if (k->max_num_nodes != p->max_num_nodes || k->num_node_types != p->num_node_types || k->num_edge_types != p->num_edge_types) return GTOK_E_INVAL;
+  }
   if (pd) {   // rows appended to a packed buffer by the walk itself: the two lane-per-graph kernels, rows that start on 16-byte boundaries
     const bool too_wide = ld > (u16 ? 2040 : 1020);         // (a row's 16-byte pieces are counted in 8 bits)
     if (which != SentKernel::Lane && which != SentKernel::BLane) return GTOK_E_UNSUPPORTED;
@@ -203,9 +210,13 @@ template <int MODE, int P, bool PK, bool U16, bool PACK, bool PK8>
 LaneKernel lane_instance() { return sent_lane_kernel<MODE != 0, P, MODE == 2, PK, U16, PACK, PK8>; }
 // p3: 4 counter planes, else 6; pk: the batch has its byte mirror; pack: the instantiations that append to the packed buffer (batches
 // with the byte mirror only), pk8: at one byte per id (16-bit rows only)
-template <int MODE> LaneKernel lane_kernel(bool p3, bool pk, bool u16, bool pack, bool pk8) {
+// tok8: gtok_sent_prepared - type bytes staged from the constants mirror (MODE 2 from the byte mirror, no packing: check_sent_args / launch_lane)
+template <int MODE> LaneKernel lane_kernel(bool p3, bool pk, bool u16, bool pack, bool pk8, bool tok8) {
   return with_flag(p3, [=](auto p3_) -> LaneKernel {
     constexpr int P = decltype(p3_)::value ? 4 : 6;
+    if constexpr (MODE == 2) {
+      if (tok8) return u16 ? sent_lane_kernel<true, P, true, true, true, false, false, true> : sent_lane_kernel<true, P, true, true, false, false, false, true>;
+    }
     if (pk8) return lane_instance<MODE, P, true, true, true, true>();
     return with_flag(u16, [=](auto u16_) -> LaneKernel {
       constexpr bool U16 = decltype(u16_)::value;
@@ -266,8 +277,11 @@ int launch_lane(const SentCall &c) {
   const bool p3 = g->max_degree > 0 && g->max_degree <= 15;
   const bool pk = g->rowptr8 && g->col8, pack = c.pd != nullptr;
   if (pack && !pk) return GTOK_E_UNSUPPORTED;
-  const LaneKernel kern = !p->labeled ? lane_kernel<0>(p3, pk, c.u16, pack, c.pk8)
-                          : p->remap_zinc ? lane_kernel<2>(p3, pk, c.u16, pack, c.pk8) : lane_kernel<1>(p3, pk, c.u16, pack, c.pk8);
+  const bool tok8 = c.consts != nullptr;
+  if (tok8 && pack) return GTOK_E_INVAL;
+  if (tok8) { a.g.nattr = c.consts->ntok8; a.g.eattr = c.consts->etok8; }   // staged where the type bytes were: same offsets, same lengths
+  const LaneKernel kern = !p->labeled ? lane_kernel<0>(p3, pk, c.u16, pack, c.pk8, false)
+                          : p->remap_zinc ? lane_kernel<2>(p3, pk, c.u16, pack, c.pk8, tok8) : lane_kernel<1>(p3, pk, c.u16, pack, c.pk8, false);
   const int ncu = device_cu_count(c.dev);
   a.units = g->unit_ptr ? g->num_units : (g->num_graphs + 63) / 64; a.epochs = K; a.pad_nt = c.pad_nt;
   if ((int64_t)a.units * K > 0x7FFFFFFF / 64) return GTOK_E_TOO_LARGE;
@@ -370,10 +384,10 @@ int launch_wave(const SentCall &c) {
 }
 
 int sent_impl(const gtok_csr *g, const gtok_sent_params *p, int32_t *out_ids, int32_t ld, int32_t *out_len,
-              const PackDest *pd, void *stream) {
+              const PackDest *pd, const gtok_sent_consts *consts, void *stream) {
   gtok::DeviceScope device_scope((hipStream_t)stream);   // the stream's device, not the thread's current one
   if (!device_scope.ok()) return GTOK_E_NO_DEVICE;
-  SentCall c{g, p, out_ids, ld, out_len, pd, (hipStream_t)stream, device_scope.dev};
+  SentCall c{g, p, out_ids, ld, out_len, pd, consts, (hipStream_t)stream, device_scope.dev};
   const int rc = check_sent_args(c);
   if (rc != GTOK_OK || c.which == SentKernel::None) return rc;       // (None: an empty batch)
   return c.which == SentKernel::BLane ? launch_blane(c) : c.which == SentKernel::Lane ? launch_lane(c) : launch_wave(c);
@@ -383,7 +397,12 @@ int sent_impl(const gtok_csr *g, const gtok_sent_params *p, int32_t *out_ids, in
 
 extern "C" int gtok_sent(const gtok_csr *g, const gtok_sent_params *p, int32_t *out_ids,
                          int32_t ld, int32_t *out_len, void *stream) {
-  return sent_impl(g, p, out_ids, ld, out_len, nullptr, stream);
+  return sent_impl(g, p, out_ids, ld, out_len, nullptr, nullptr, stream);
+}
+
+extern "C" int gtok_sent_prepared(const gtok_csr *g, const gtok_sent_params *p, const gtok_sent_consts *consts, int32_t *out_ids,
+                                  int32_t ld, int32_t *out_len, void *stream) {
+  return sent_impl(g, p, out_ids, ld, out_len, nullptr, consts, stream);
 }
 
 extern "C" int gtok_sent_packed(const gtok_csr *g, const gtok_sent_params *p, int32_t *out_ids, int32_t ld, int32_t *out_len,
@@ -391,7 +410,7 @@ extern "C" int gtok_sent_packed(const gtok_csr *g, const gtok_sent_params *p, in
   if (!g || !p) return GTOK_E_INVAL;
   if (g->num_graphs == 0) return GTOK_OK;
   const PackDest pk{packed, capacity, row_start, state};
-  return sent_impl(g, p, out_ids, ld, out_len, &pk, stream);
+  return sent_impl(g, p, out_ids, ld, out_len, &pk, nullptr, stream);
 }
 
 extern "C" int64_t gtok_sent_pack_scratch_rows(void *stream) {

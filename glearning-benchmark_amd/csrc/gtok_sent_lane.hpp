@@ -201,7 +201,10 @@ struct SentLaneArgs {
 // kernel's register allocation is not to be touched)
 // PK8: GTOK_SENT_PACK_U8 (with U16 and PACK only) - the packed buffer holds ONE byte per id: the copy at a unit's end narrows two
 // 16-byte pieces of a staged row into one.  Every line of it sits behind `if constexpr`: the other instantiations are untouched
-template <bool LAB, int P, bool REMAP, bool PK, bool U16, bool PACK = false, bool PK8 = false>
+// TOK8: gtok_sent_prepared (with LAB, REMAP and PK only) - the launcher has put the constants mirror (ntok8 / etok8: the remapped
+// token of every type byte, gtok_sent_lane_consts) where nattr / eattr stand in `a.g`, so seat and snat are staged from it and a
+// staged byte IS the token: no range compares and no add per node type, trail edge and bracket member.  Behind `if constexpr` too
+template <bool LAB, int P, bool REMAP, bool PK, bool U16, bool PACK = false, bool PK8 = false, bool TOK8 = false>
 __global__ void __launch_bounds__(1024) sent_lane_kernel(const SentLaneArgs a) {
   using out_t = typename std::conditional<U16, uint16_t, int32_t>::type;
   constexpr int EV = U16 ? 8 : 4;            // ids per 16-byte store
@@ -224,6 +227,7 @@ __global__ void __launch_bounds__(1024) sent_lane_kernel(const SentLaneArgs a) {
   asm volatile("v_mov_b32 %0, %1" : "=v"(k1) : "s"((uint32_t)(a.p.seed >> 32)));
   const uint32_t epoch0 = (uint32_t)a.p.epoch;
   constexpr bool remap = REMAP;             // folded into the emission constants (host guarantees maxn <= max_num_nodes)
+  static_assert(!TOK8 || (LAB && REMAP && PK), "the constants mirror holds remapped type tokens and is staged as bytes");
   const int pos_base = remap ? 22 : idx_off;
   const uint64_t T_RESET = remap ? 2 : GTOK_SENT_RESET, T_LADJ = remap ? 2 : GTOK_SENT_LADJ;
   const uint64_t T_RADJ = remap ? 2 : GTOK_SENT_RADJ, T_EOS = remap ? 1 : GTOK_SENT_EOS;
@@ -708,8 +712,14 @@ __global__ void __launch_bounds__(1024) sent_lane_kernel(const SentLaneArgs a) {
             uint32_t lo = tpos, hi = 0;                          // token pair, then the third token
             int cnt = 1;
             if (LAB) {
-              if (kind == 0) { ta = remap ? remap_edge_type_u(et, (uint32_t)edge_off) : (uint32_t)edge_off + et; has_a = true; }
-              const uint32_t ty = remap ? remap_node_type_u(xb, (uint32_t)node_off, (uint32_t)a.p.num_node_types) : (uint32_t)node_off + xb;
+              if (kind == 0) {
+                if constexpr (TOK8) ta = et;               // the staged byte is the token
+                else ta = remap ? remap_edge_type_u(et, (uint32_t)edge_off) : (uint32_t)edge_off + et;
+                has_a = true;
+              }
+              uint32_t ty;
+              if constexpr (TOK8) ty = xb;
+              else ty = remap ? remap_node_type_u(xb, (uint32_t)node_off, (uint32_t)a.p.num_node_types) : (uint32_t)node_off + xb;
               lo |= first ? ty << 16 : 0u;
               cnt += first;
             }
@@ -741,7 +751,9 @@ __global__ void __launch_bounds__(1024) sent_lane_kernel(const SentLaneArgs a) {
               const uint64_t tp = (uint64_t)(pos_base + (int)snat[nbase + u]);
               if (LAB) {
                 const uint32_t at = find_et(rc, (uint32_t)u);
-                const uint64_t te = remap ? remap_edge_type_u(at, (uint32_t)edge_off) : (uint32_t)edge_off + at;
+                uint64_t te;
+                if constexpr (TOK8) te = at;
+                else te = remap ? remap_edge_type_u(at, (uint32_t)edge_off) : (uint32_t)edge_off + at;
                 append((uint64_t)T_LADJ | (te << 16) | (tp << 32) | (T_RADJ << 48), 4);
               } else {
                 append((uint64_t)T_LADJ | (tp << 16) | (T_RADJ << 32), 3);
@@ -762,7 +774,8 @@ __global__ void __launch_bounds__(1024) sent_lane_kernel(const SentLaneArgs a) {
                 int cnt = 1;
                 if (LAB) {
                   const uint32_t at = find_et(rc, (uint32_t)bu);
-                  lo = (remap ? remap_edge_type_u(at, (uint32_t)edge_off) : (uint32_t)edge_off + at) | (lo << 16);
+                  if constexpr (TOK8) lo = at | (lo << 16);
+                  else lo = (remap ? remap_edge_type_u(at, (uint32_t)edge_off) : (uint32_t)edge_off + at) | (lo << 16);
                   cnt = 2;
                 }
                 if (head) { hi = lo >> 16; lo = (uint32_t)T_LADJ | (lo << 16); ++cnt; head = false; }

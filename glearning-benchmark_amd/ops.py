@@ -539,15 +539,21 @@ def sent(batch: GraphBatch, max_num_nodes: int, max_len: int, seed: int, epoch: 
     params = lambda flags: _sent_params(max_num_nodes, max_len, labeled, num_node_types, num_edge_types, remap_zinc, pad_id, flags,
                                         seed, epoch, graph_base, query, K)
     p = params((0 if pad else _lib.SENT_NO_PAD) | (_lib.SENT_U16 if u16 else 0))
-    cs = _sent_layouts(batch, p, max_len)
-    global _LAST_SENT
-    _LAST_SENT = (cs, p)
+    cs, lb = _sent_layouts(batch, p, max_len)
+    global _LAST_SENT, _LAST_CONSTS
+    _LAST_SENT, _LAST_CONSTS = (cs, p), False
     rc = _lib.E_UNSUPPORTED if packed is None else _sent_packed(cs, p, params, packed, ids, staging, ln, K * G, ld, u16, dev)
     if rc == _lib.E_UNSUPPORTED:
         if ids is None:             # another kernel walks: it needs the slab after all (a temporary one)
             ids = torch.empty((K * G, ld), dtype=torch.int16 if u16 else torch.int32, device=dev)
-        check(lib().gtok_sent(ctypes.byref(cs), ctypes.byref(p), ids.data_ptr(), ld, ln.data_ptr(), _stream(dev)),
-              "gtok_sent")
+        kc = _sent_consts(lb, p) if lb is not None and labeled and remap_zinc else None
+        if kc is not None:          # the reordered batch's constants mirror: the walk emits staged bytes as tokens
+            check(lib().gtok_sent_prepared(ctypes.byref(cs), ctypes.byref(p), ctypes.byref(kc), ids.data_ptr(), ld, ln.data_ptr(), _stream(dev)),
+                  "gtok_sent_prepared")
+            _LAST_CONSTS = True
+        else:
+            check(lib().gtok_sent(ctypes.byref(cs), ctypes.byref(p), ids.data_ptr(), ld, ln.data_ptr(), _stream(dev)),
+                  "gtok_sent")
         if packed is not None and G:           # another kernel walked: the one-pass pack behind it (dataset order)
             _pack_behind_walk(packed, ids, ln, K * G, ld, dev)
     if packed is not None and packed.buf.dtype == torch.uint8 and check_ids and G and not torch.cuda.is_current_stream_capturing():
@@ -698,8 +704,47 @@ def _mirror_wanted(cs: _lib.GtokCsr, p: GtokSentParams) -> bool:
     return lib().gtok_sent_kernel_name(ctypes.byref(claim), ctypes.byref(p)).startswith(b"sent_blane_kernel")
 
 
-def _sent_layouts(batch: GraphBatch, p: GtokSentParams, max_len: int) -> _lib.GtokCsr:
-    """The C struct sent() launches: the batch with the layouts its kernel reads, each built on first use and kept on the batch."""
+def lane_consts(sb: GraphBatch, max_num_nodes: int, num_node_types: int, num_edge_types: int) -> Optional[dict]:
+    """The constants mirror of a reordered batch (ops.lane_sorted's copy, or a caller-prepared one) for one set of tokenizer
+    settings, built by gtok_sent_lane_consts on first use and kept on the batch, one per settings key: ntok8 / etok8 - the
+    remapped token of every node / entry type byte, which the labelled + remapped walk stages in place of the bytes - and
+    `status` (the ONE host read of the build; non-zero: a token does not fit a byte and `consts`, the C struct gtok_sent_prepared
+    takes, is None).  A layout step like lane_sorted, never part of an epoch.  None: not such a batch, or a library without it."""
+    if sb.graph_ids is None or sb.unit_ptr is None or sb.rowptr8 is None or sb.col8 is None or sb.nattr is None or sb.eattr is None \
+            or sb.col.device.type != "cuda" or not hasattr(lib(), "gtok_sent_prepared"):
+        return None
+    key = (int(max_num_nodes), int(num_node_types), int(num_edge_types))
+    hit = sb.lane_consts.get(key)
+    if hit is None:
+        if torch.cuda.is_current_stream_capturing():      # (the status read-back cannot be captured: this launch goes without)
+            return None
+        dev, N, E = sb.device, sb.num_nodes_total, sb.num_edges_total
+        ntok8 = torch.empty(N + 16, dtype=torch.uint8, device=dev)      # (+ 16: the slack the byte mirrors carry)
+        etok8 = torch.empty(E + 16, dtype=torch.uint8, device=dev)
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        p = _sent_params(key[0], 0, True, key[1], key[2], True)
+        cs = sb.c_struct()
+        check(lib().gtok_sent_lane_consts(ctypes.byref(cs), ctypes.byref(p), N, E, ntok8.data_ptr(), etok8.data_ptr(), status.data_ptr(),
+                                          _stream(dev)), "gtok_sent_lane_consts")
+        st = int(status.item())
+        c = None if st else _lib.GtokSentConsts(ntok8.data_ptr(), etok8.data_ptr(), key[0], key[1], key[2], 0)
+        hit = sb.lane_consts[key] = dict(ntok8=ntok8[:N], etok8=etok8[:E], status=st, consts=c)   # (item assignment: the cached C struct stays)
+    return hit
+
+
+def _sent_consts(lb: GraphBatch, p: GtokSentParams):
+    """gtok_sent_consts for this launch of the reordered batch `lb`, or None (switched off, not applicable, a token beyond a byte)."""
+    if os.environ.get("GTOK_NO_LANE_CONSTS") == "1":       # tests, A/B
+        return None
+    hit = lb.lane_consts.get((p.max_num_nodes, p.num_node_types, p.num_edge_types))
+    if hit is None:
+        hit = lane_consts(lb, p.max_num_nodes, p.num_node_types, p.num_edge_types)
+    return None if hit is None else hit["consts"]
+
+
+def _sent_layouts(batch: GraphBatch, p: GtokSentParams, max_len: int):
+    """(the C struct sent() launches: the batch with the layouts its kernel reads, each built on first use and kept on the batch;
+    the reordered batch behind it - ops.lane_sorted's copy or the caller's own - or None)"""
     if not batch.prepared:          # (a batch prepared by the caller - torch.ops.gtok.csr_prepare - is launched as it stands)
         pack8(batch)
         # the bit-matrix mirror is only built where gtok_sent would pick the kernel that reads it - and never again for a batch
@@ -715,8 +760,8 @@ def _sent_layouts(batch: GraphBatch, p: GtokSentParams, max_len: int) -> _lib.Gt
             and lib().gtok_sent_kernel_name(ctypes.byref(cs), ctypes.byref(p)) == b"sent_lane_kernel":
         sb = lane_sorted(batch)                                       # once per resident batch
         if sb is not None:
-            cs = sb.c_struct()
-    return cs
+            return sb.c_struct(), sb
+    return cs, (batch if batch.graph_ids is not None else None)
 
 
 def _sent_packed(cs, p: GtokSentParams, params, packed: PackedRows, ids, staging, ln, rows: int, ld: int, u16: bool, dev) -> int:
@@ -784,6 +829,13 @@ def _pack_scratch(dev, ld: int, u16: bool) -> torch.Tensor:
 
 
 _LAST_SENT = None
+_LAST_CONSTS = False
+
+
+def last_sent_consts() -> bool:
+    """Whether the most recent ops.sent call launched the instantiation that reads the constants mirror (gtok_sent_prepared:
+    sent_lane_kernel<..., TOK8>).  last_sent_kernel() names the kernel template either way."""
+    return bool(_LAST_CONSTS) and not isinstance(_LAST_SENT, str)
 
 
 def last_sent_kernel() -> str:

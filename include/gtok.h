@@ -402,6 +402,37 @@ typedef struct gtok_sent_params {
 int gtok_sent(const gtok_csr *g, const gtok_sent_params *p, int32_t *out_ids,
               int32_t ld, int32_t *out_len, void *stream);
 
+/* ---- the constants mirror of a reordered batch: what the lane-per-graph walk would otherwise recompute in every epoch ---------
+ * A labelled walk with the ZINC remap turns every attribute byte it visits into a token, and the result depends only on the byte
+ * and on (max_num_nodes, num_node_types, num_edge_types) - settings a tokenizer fixes for the life of a dataset.  The mirror
+ * holds those tokens, computed once per resident batch and settings:
+ *   ntok8[N]  the token of every node type:  gtok_sent's remapped node-type token of nattr[i]
+ *   etok8[E]  the token of every entry type: gtok_sent's remapped edge-type token of eattr[i]
+ * indexed as nattr / eattr of the SAME (reordered) batch; the kernel stages them in place of the attribute bytes and emits a
+ * byte as it stands (no range compare, no add per token).  gtok_sent_lane_consts builds the two arrays (device memory,
+ * caller-allocated: num_nodes / num_entries bytes, the batch's node and entry totals) with a thread per byte and zeroes *status
+ * (int32, device memory) first; bit 0 of it is set when a token does not fit a byte (an attribute of 255, a large
+ * max_num_nodes): the mirror must then not be used.  The caller reads the status back once, at build time.  The builder reads
+ * nattr / eattr below the two totals only, and nothing through an offset.  GTOK_E_INVAL: null pointers, negative totals, a
+ * batch without graph_ids / unit_ptr or without attributes, p not labelled with remap_zinc.  (Added without an ABI version
+ * step: no struct changes - a library may lack the two entry points.)
+ * gtok_sent_prepared is gtok_sent with the mirror: consts == NULL is gtok_sent itself; otherwise GTOK_E_INVAL unless the batch
+ * runs the lane-per-graph kernel from its byte mirror (graph_ids, unit_ptr, rowptr8, col8), p is labelled with remap_zinc and
+ * p's three settings equal the recorded ones.  The arrays are only ever read as token VALUES, at the offsets nattr / eattr are
+ * read at: a stale mirror gives wrong tokens and never widens what the kernel addresses.                                     */
+typedef struct gtok_sent_consts {
+  const uint8_t *ntok8;
+  const uint8_t *etok8;
+  int32_t max_num_nodes;  /* the settings the mirror was built for */
+  int32_t num_node_types;
+  int32_t num_edge_types;
+  int32_t reserved;       /* must be 0 */
+} gtok_sent_consts;
+int gtok_sent_lane_consts(const gtok_csr *g, const gtok_sent_params *p, int64_t num_nodes, int64_t num_entries, uint8_t *ntok8,
+                          uint8_t *etok8, int32_t *status, void *stream);
+int gtok_sent_prepared(const gtok_csr *g, const gtok_sent_params *p, const gtok_sent_consts *consts, int32_t *out_ids,
+                       int32_t ld, int32_t *out_len, void *stream);
+
 /* ---- gtok_sent_large: the SENT walk for graphs of more than GTOK_MAX_NODES nodes -------------------------------------------
  * Same spec, same tokens, same output convention as gtok_sent (bit-exact against oracle_sent), for ANY batch in dataset order
  * whose largest graph has at most GTOK_SENT_LARGE_MAX_NODES nodes - small graphs included, so a caller need not split a

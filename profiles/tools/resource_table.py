@@ -26,13 +26,13 @@ def parse(path):
 
 
 def targs(name):
-    """template arguments of a mangled kernel name: Li4E -> 4, Lb1E -> 1; a missing trailing default (PACK, PK8) -> 0"""
+    """template arguments of a mangled kernel name: Li4E -> 4, Lb1E -> 1; a missing trailing default (PACK, PK8, TOK8) -> 0"""
     return [x[2:-1] for x in re.findall(r"L[ib]\d+E", name)]
 
 
 def main():
     parent, branch = parse(sys.argv[1]), parse(sys.argv[2])
-    for kern, cols, n in (("sent_blane_kernel", "W P U16 PACK", 4), ("sent_lane_kernel", "LAB P REMAP PK U16 PACK PK8", 7)):
+    for kern, cols, n in (("sent_blane_kernel", "W P U16 PACK", 4), ("sent_lane_kernel", "LAB P REMAP PK U16 PACK PK8 TOK8", 8)):
         print(f"## `{kern}`\n")
         print(f"| {cols} | VGPRs | AGPRs | SGPRs (total) | scratch bytes / lane | waves / SIMD | static LDS | SGPR spills | VGPR spills | against the parent |")
         print("|---|---|---|---|---|---|---|---|---|---|")
@@ -42,7 +42,7 @@ def main():
             a = targs(name)
             a += ["0"] * (n - len(a))
             # the parent's name of the same instantiation: a trailing `false` default was not spelled there
-            old = parent.get(name) or parent.get(re.sub(r"Lb0E(E+vNS_\d+SentBLaneArgsE)$", r"\1", name))
+            old = parent.get(name) or parent.get(re.sub(r"Lb0E(E+vNS_\d+Sent\w+ArgsE)$", r"\1", name))
             verdict = "new" if old is None else ("identical" if all(old.get(f) == r.get(f) for f in FIELDS) else
                                                  "CHANGED: " + ", ".join(f"{f} {old.get(f)} -> {r.get(f)}" for f in FIELDS if old.get(f) != r.get(f)))
             print("| " + " ".join(a) + " | " + " | ".join(r.get(f, "?") for f in FIELDS) + f" | {verdict} |")
