@@ -11,10 +11,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 # GTOK_LIB: load another build of the same ABI (profiling builds of profiles/tools, e.g. -DGTOK_PHASE_TIMING)
 LIB_PATH = os.environ.get("GTOK_LIB") or os.path.join(_HERE, "csrc", "libgtok.so")
-SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("gtok_sent.hip", "gtok_sent_large.hip", "gtok_sent_decode.hip", "gtok_ibtt.hip", "gtok_ibtt_decode.hip", "gtok_csr_relabel.hip", "gtok_graph_tasks.hip", "gtok_graph_keys.hip", "gtok_text.hip", "gtok_rows.hip", "gtok_csr.hip")]
+SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("gtok_sent.hip", "gtok_sent_large.hip", "gtok_sent_decode.hip", "gtok_ibtt.hip", "gtok_ibtt_decode.hip", "gtok_csr_relabel.hip", "gtok_graph_tasks.hip", "gtok_graph_keys.hip", "gtok_graph_wl.hip", "gtok_text.hip", "gtok_rows.hip", "gtok_csr.hip")]
 HEADERS = [os.path.join(_HERE, "csrc", h) for h in ("gtok_common.hpp", "gtok_sent_blane.hpp", "gtok_sent_reg.hpp", "gtok_sent_lds.hpp", "gtok_sent_lane.hpp",
                                                    "gtok_decode_args.hpp", "gtok_decode_csr.hpp", "gtok_csr_relabel_args.hpp", "gtok_zinc_unremap.hpp", "gtok_graph_tasks_args.hpp",
-                                                   "gtok_graph_keys_args.hpp", "gtok_graph_keys_hash.hpp")] \
+                                                   "gtok_graph_keys_args.hpp", "gtok_graph_keys_hash.hpp", "gtok_graph_wl_args.hpp", "gtok_graph_wl_hash.hpp")] \
           + [os.path.join(_ROOT, "include", "gtok.h")]
 
 c_i32p = ctypes.POINTER(ctypes.c_int32)
@@ -128,6 +128,8 @@ SYMBOLS = {
     "gtok_csr_relabel": (_I, [ctypes.POINTER(GtokCsr), _P, _I, _P, ctypes.POINTER(GtokCsrBuilt), _P, _P, ctypes.c_int64, _P]),
     "gtok_graph_tasks": (_I, [ctypes.POINTER(GtokCsr), _P, _P, ctypes.c_int64, _P, _P, _P, _P, _P]),
     "gtok_graph_keys": (_I, [ctypes.POINTER(GtokCsr), _P, _I, _P, _P, _P]),
+    "gtok_graph_wl_workspace": (ctypes.c_int64, [_I, _I]),
+    "gtok_graph_wl": (_I, [ctypes.POINTER(GtokCsr), _P, _I, _I, _P, _P, _P, _P, ctypes.c_int64, _P]),
     "gtok_remap_zinc": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P]),
     "gtok_collate": (_I, [_P, _I, _P, _P, _I, _I, _P, _P, _I, _P, _P]),
     "gtok_parse_graph_text": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
@@ -170,10 +172,12 @@ ORDER_SYMBOLS = ("gtok_sent_large_order", "gtok_csr_relabel_workspace", "gtok_cs
 ZINC_DECODE_SYMBOLS = ("gtok_unremap_zinc", "gtok_sent_decode_zinc_sizes", "gtok_sent_decode_zinc_csr")   # likewise (ops.sent_decode_zinc_csr)
 GRAPH_TASKS_SYMBOLS = ("gtok_graph_tasks",)                                 # likewise (ops.graph_tasks)
 GRAPH_KEYS_SYMBOLS = ("gtok_graph_keys",)                                   # likewise (ops.graph_keys)
+GRAPH_WL_SYMBOLS = ("gtok_graph_wl_workspace", "gtok_graph_wl")             # likewise (ops.graph_wl_keys)
 LANE_CONSTS_SYMBOLS = ("gtok_sent_lane_consts", "gtok_sent_prepared")       # likewise (ops.lane_consts; ops.sent goes without)
 _MAY_BE_MISSING = frozenset(OPTIONAL_SYMBOLS + DECODE_CSR_SYMBOLS + IBTT_DECODE_SYMBOLS + ORDER_SYMBOLS + ZINC_DECODE_SYMBOLS + GRAPH_TASKS_SYMBOLS
-                            + GRAPH_KEYS_SYMBOLS + LANE_CONSTS_SYMBOLS)
+                            + GRAPH_KEYS_SYMBOLS + GRAPH_WL_SYMBOLS + LANE_CONSTS_SYMBOLS)
 KEYS_LISTED, KEYS_CLOSURE, KEYS_ATTRS = 0, 1, 2                             # include/gtok.h: GTOK_KEYS_*
+WL_ATTRS, WL_MAX_ROUNDS, WL_LARGE_WAVES = 2, 512, 1024                       # include/gtok.h: GTOK_WL_*
 IBTT_GRAMMAR_ZINC, IBTT_GRAMMAR_SYNTH = 0, 1                                # include/gtok.h: GTOK_IBTT_GRAMMAR_*
 
 ERRORS = {-1: "GTOK_E_INVAL", -2: "GTOK_E_TOO_LARGE", -3: "GTOK_E_LAUNCH", -4: "GTOK_E_NO_DEVICE", -5: "GTOK_E_GRAPH_SLOTS", -6: "GTOK_E_UNSUPPORTED"}

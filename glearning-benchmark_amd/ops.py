@@ -1499,10 +1499,12 @@ def _group_by_keys(keys: torch.Tensor) -> torch.Tensor:
     return group
 
 
-def _canonical_lists(bl, ptr, gs: torch.Tensor, closure: bool, attrs: bool):
+def _canonical_lists(bl, ptr, gs: torch.Tensor, closure: bool, attrs: bool, rank=None):
     """The canonical folded entry lists of the graphs `gs` (sorted indices into the concatenation): (graph slot, a, b, t) packed into
     int64, sorted (closure: distinct) -> (vals = the packed (a, b, t), starts, counts per slot); with attrs also the node bytes the same
-    way.  Torch gathers over the chosen graphs only."""
+    way.  Torch gathers over the chosen graphs only.  rank (ops.isomorphic_duplicates): one int64 [N] per batch, a numbering of every
+    graph's nodes that replaces the stored one - the entries are renumbered through it and, with attrs, kept DIRECTED (row, column:
+    each direction of a symmetric listing carries its own byte) and the node bytes are laid out in the new numbering."""
     dev = gs.device
     K = int(gs.numel())
     packed, nvals = [], []
@@ -1524,9 +1526,16 @@ def _canonical_lists(bl, ptr, gs: torch.Tensor, closure: bool, attrs: bool):
         u, c = node_loc[je], b.col[ent].to(torch.int64)
         t = b.eattr[ent].to(torch.int64) if attrs else torch.zeros_like(u)
         slot = sel[jn][je]
-        packed.append((((slot << 14 | torch.minimum(u, c)) << 14 | torch.maximum(u, c)) << 8) | t)
+        if rank is not None:
+            base = nptr[l][jn]
+            u, c = rank[s][base + node_loc][je], rank[s][base[je] + c]
+        lo, hi = (u, c) if rank is not None and attrs else (torch.minimum(u, c), torch.maximum(u, c))
+        packed.append((((slot << 14 | lo) << 14 | hi) << 8) | t)
         if attrs:
-            nvals.append(b.nattr[nptr[l][jn] + node_loc].to(torch.int64))
+            nv = b.nattr[nptr[l][jn] + node_loc].to(torch.int64)
+            if rank is not None:              # node k of the new numbering: the node whose rank is k
+                nv = torch.empty_like(nv).scatter_(0, (torch.cumsum(nc, 0) - nc)[jn] + rank[s][nptr[l][jn] + node_loc], nv)
+            nvals.append(nv)
     vals = torch.sort(torch.cat(packed)).values if packed else torch.zeros(0, dtype=torch.int64, device=dev)
     if closure:
         vals = torch.unique_consecutive(vals)
@@ -1673,6 +1682,257 @@ def split_leakage(splits: Dict[str, object], mode: str = "listed", attrs: bool =
         out["example"][key] = (ia - dup.split_ptr[a], ib - dup.split_ptr[b]) if ovh[a][b] else None
     out["leakage"] = any(out["overlap"].values())
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# numbering-independent keys: Weisfeiler-Lehman colour refinement (include/gtok.h: gtok_graph_wl)
+# ------------------------------------------------------------------------------------------------
+WL_MAX_NODES_ANY = 512         # beyond it the kernel pulls over the CSR rows and needs GTOK_CSR_SIMPLE_SYMMETRIC; rounds=0 ends here
+_WL_WS = {}
+
+
+def _wl_workspace(dev, need: int) -> torch.Tensor:
+    """gtok_graph_wl's workspace (graphs of more than 4,096 nodes only): one uint8 buffer per device, grown on demand, as
+    _large_workspace keeps gtok_sent_large's"""
+    key = torch.device(dev).index or 0
+    t = _WL_WS.get(key)
+    if t is None or t.numel() < need:
+        t = torch.empty(max(16, need), dtype=torch.uint8, device=dev)
+        _WL_WS[key] = t
+    return t
+
+
+def _wl_flags(batches, rounds: int, attrs: bool) -> int:
+    """GTOK_WL_* of attrs; the argument errors that need no device"""
+    if not 0 <= int(rounds) <= _lib.WL_MAX_ROUNDS:
+        raise ValueError(f"graph_wl_keys: rounds must be in [0, {_lib.WL_MAX_ROUNDS}] (0 = as many rounds as the graph has nodes) (GTOK_E_INVAL)")
+    for b in batches:
+        if attrs and (b.nattr is None or b.eattr is None):
+            raise ValueError("graph_wl_keys: attrs=True needs a batch with node and edge attributes (GTOK_E_INVAL)")
+        if b.graph_ids is not None:
+            raise ValueError("graph_wl_keys: a batch in dataset order only (not ops.lane_sorted's copy)")
+    return _lib.WL_ATTRS if attrs else 0
+
+
+def _graph_wl_launch(batch: GraphBatch, labels: Optional[torch.Tensor], rounds: int, flags: int, with_colors: bool,
+                     info: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """gtok_graph_wl on the current stream -> (keys int64 [G, 2], colours int64 [N] or None, info int32 [4]); no host read."""
+    _need_gpu(batch.col, "graph_wl_keys")
+    _need(_lib.GRAPH_WL_SYMBOLS, "gtok_graph_wl")
+    dev, G = batch.device, batch.num_graphs
+    sym = bool(batch.flags & _lib.CSR_SIMPLE_SYMMETRIC)
+    if batch.max_nodes > _lib.SENT_LARGE_MAX_NODES:
+        raise _lib.GtokError(f"graph_wl_keys: a graph of {batch.max_nodes} nodes is beyond the {_lib.SENT_LARGE_MAX_NODES} the kernels hold "
+                             "(GTOK_E_TOO_LARGE)")
+    if batch.max_nodes > WL_MAX_NODES_ANY and not sym:
+        raise _lib.GtokError(f"graph_wl_keys: graphs of more than {WL_MAX_NODES_ANY} nodes (this batch: {batch.max_nodes}) are refined over the "
+                             "CSR rows themselves, which must list every edge once in each direction, without loops: the batch does not "
+                             "carry GTOK_CSR_SIMPLE_SYMMETRIC (GTOK_E_UNSUPPORTED)")
+    if (flags & _lib.WL_ATTRS) and not sym and G:
+        raise _lib.GtokError("graph_wl_keys: attrs=True reads each direction's own attribute byte off the CSR rows: the batch does not carry "
+                             "GTOK_CSR_SIMPLE_SYMMETRIC (GTOK_E_UNSUPPORTED)")
+    if rounds == 0 and batch.max_nodes > WL_MAX_NODES_ANY:
+        raise _lib.GtokError(f"graph_wl_keys: rounds=0 runs as many rounds as a graph has nodes and ends at {WL_MAX_NODES_ANY} nodes (this "
+                             f"batch: {batch.max_nodes}): give a round count (GTOK_E_UNSUPPORTED)")
+    labels = _labels_of(batch, labels, dev)
+    if info is None:
+        info = torch.zeros(4, dtype=torch.int32, device=dev)
+    elif info.dtype != torch.int32 or info.numel() != 4 or info.device != dev or not info.is_contiguous():
+        raise ValueError("graph_wl_keys: info must be int32 [4] on the batch's device")
+    keys = torch.empty((G, 2), dtype=torch.int64, device=dev)
+    colors = torch.zeros(batch.num_nodes_total, dtype=torch.int64, device=dev) if with_colors else None
+    if G == 0:
+        return keys, colors, info
+    need = int(lib().gtok_graph_wl_workspace(batch.max_nodes, G))
+    if need < 0:
+        check(need, "gtok_graph_wl_workspace")
+    ws = None
+    if need > 0:
+        ws = workspace if workspace is not None else _wl_workspace(dev, need)
+        if ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.device != torch.device(dev):
+            raise ValueError("workspace: a contiguous uint8 tensor on the batch's device")
+    cs = batch.c_struct()
+    check(lib().gtok_graph_wl(ctypes.byref(cs), None if labels is None else labels.data_ptr(), int(rounds), flags, keys.data_ptr(),
+                              None if colors is None else colors.data_ptr(), info.data_ptr(), None if ws is None else ws.data_ptr(),
+                              0 if ws is None else ws.numel(), _stream(dev)), "gtok_graph_wl")
+    return keys, colors, info
+
+
+def graph_wl_keys(batch: GraphBatch, rounds: int = 3, labels: Optional[torch.Tensor] = None, attrs: bool = False,
+                  with_colors: bool = False, info: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """gtok_graph_wl: a 128-bit key per graph that does NOT depend on its numbering -> int64 [G, 2] on the device (the two uint64 words,
+    bit for bit); with_colors=True: (keys, colours int64 [N]), the final colour of every node (a damaged graph's stay 0).  The key is
+    that of `rounds` rounds of Weisfeiler-Lehman colour refinement over the simple undirected closure of the listed entries (rounds=0: as
+    many rounds as the graph has nodes, up to 512 nodes): isomorphic graphs always share it - the same molecule decoded from two epochs'
+    token rows, a renumbered, re-oriented or re-listed copy.  It is an invariant, not an isomorphism class: graphs colour refinement
+    cannot tell apart (regular graphs of equal degree) share it too, and 128 bits can collide; ops.isomorphic_duplicates confirms what
+    can be confirmed.  attrs=True: node and edge attribute bytes enter the colours (GTOK_CSR_SIMPLE_SYMMETRIC batches only, as are
+    graphs of more than 512 nodes).  labels int32 [G] or None; info: an int32 [4] tensor of the caller's to accumulate the status into
+    (bit KEYS_DAMAGED, the damaged graphs); workspace: a uint8 tensor of the caller's own (graphs of more than 4,096 nodes; launches on
+    several streams must not share the module's), None = a cached one per device."""
+    flags = _wl_flags([batch], rounds, attrs)
+    keys, colors, _ = _graph_wl_launch(batch, labels, int(rounds), flags, with_colors, info, workspace)
+    return (keys, colors) if with_colors else keys
+
+
+class IsoDuplicates(Duplicates):
+    """What ops.isomorphic_duplicates returns: Duplicates (group, split, is_first, split_ptr; overlap / leaked / unique_per_split) plus
+    proven bool [T]: graph i IS isomorphic to the first graph of its class (the first itself: True).  proven = False means
+    "WL-equivalent" - no round of colour refinement tells the two apart - not "isomorphic"."""
+    __slots__ = ("proven",)
+
+    def __init__(self, group, split, is_first, split_ptr, proven):
+        super().__init__(group, split, is_first, split_ptr)
+        self.proven = proven
+
+
+def _wl_ranks(bl, colors: torch.Tensor):
+    """The nodes of the concatenation sorted by (graph, colour) -> (sorted colours, rank of every node inside its graph, one int64 [N]
+    per batch; discrete bool [T]: the graph's N colours are distinct, so the ranks number it canonically; node starts, node counts)"""
+    dev = colors.device
+    n_all = torch.cat([b.node_counts().to(torch.int64) for b in bl])
+    T, N = int(n_all.numel()), int(colors.numel())
+    gid = torch.repeat_interleave(torch.arange(T, device=dev), n_all)
+    starts = torch.cumsum(n_all, 0) - n_all
+    o1 = torch.sort(colors, stable=True).indices
+    order = o1[torch.sort(gid[o1], stable=True).indices]
+    cs = colors[order]
+    rank = torch.empty(N, dtype=torch.int64, device=dev)
+    rank[order] = torch.arange(N, device=dev) - starts[gid]              # (gid is sorted: gid[order] == gid)
+    rep = torch.zeros(T, dtype=torch.int64, device=dev)
+    if N > 1:
+        same = (cs[1:] == cs[:-1]) & (gid[1:] == gid[:-1])
+        rep.index_add_(0, gid[1:], same.to(torch.int64))
+    sizes = [b.num_nodes_total for b in bl]
+    return cs, list(torch.split(rank, sizes)), rep == 0, starts, n_all
+
+
+def _confirm_wl(bl, ll, ptr, group: torch.Tensor, colors: torch.Tensor, attrs: bool, budget_bytes: int):
+    """Classes by key -> (classes, proven).  Every member of a class of two or more is compared with the class's first member: N, the
+    label and the sorted colours (what the key digests: a member that differs there is a digest collision and leaves the class); where
+    both colourings are discrete, the entry lists (and, with attrs, the node bytes) in the numbering the colour ranks give - equal
+    lists prove the isomorphism, different ones split the member off.  The first member split off heads a new class and the others are
+    compared with it in the next round, as in _confirm_groups."""
+    dev, T = group.device, int(group.numel())
+    ar = torch.arange(T, device=dev)
+    cs, rank, discrete, nstart, n_all = _wl_ranks(bl, colors)
+    e_all = torch.cat([b.edge_ptr[1:] - b.edge_ptr[:-1] for b in bl])
+    lab = torch.cat([torch.zeros(b.num_graphs, dtype=torch.int32, device=dev) if l is None else l for b, l in zip(bl, ll)])
+    per_chunk = max(1, int(budget_bytes) // 64)
+    group = group.clone()
+    proven = group == ar
+    pending = ~proven
+    while True:
+        mem = pending.nonzero().reshape(-1)
+        if mem.numel() == 0:
+            break
+        heads = group[mem]
+        ok = (n_all[mem] == n_all[heads]) & (lab[mem] == lab[heads]) & (discrete[mem] == discrete[heads])
+        ok &= _segments_equal(cs, nstart, n_all, mem, heads)
+        sure = torch.zeros_like(ok)
+        cand = (ok & discrete[mem]).nonzero().reshape(-1)                   # the pairs whose lists can be compared
+        if cand.numel():
+            cm, ch = mem[cand], heads[cand]
+            cost = e_all[cm] + e_all[ch] + (n_all[cm] + n_all[ch] if attrs else 0) + 1
+            chunk = (torch.cumsum(cost, 0) - cost) // per_chunk
+            sizes = torch.unique_consecutive(chunk, return_counts=True)[1].tolist()
+            eq_all = torch.ones(int(cand.numel()), dtype=torch.bool, device=dev)
+            i0 = 0
+            for sz in sizes:
+                gs, inv = torch.unique(torch.cat([cm[i0:i0 + sz], ch[i0:i0 + sz]]), return_inverse=True)
+                eq = torch.ones(sz, dtype=torch.bool, device=dev)
+                for vals, starts, cnts in _canonical_lists(bl, ptr, gs, not attrs, attrs, rank):
+                    eq &= _segments_equal(vals, starts, cnts, inv[:sz], inv[sz:])
+                eq_all[i0:i0 + sz] = eq
+                i0 += sz
+            sure[cand] = eq_all
+            ok[cand] = eq_all
+        proven[mem[sure]] = True
+        pending[mem[ok]] = False
+        bad = mem[~ok]
+        if bad.numel() == 0:
+            break
+        first_bad = torch.full((T,), T, dtype=torch.int64, device=dev).scatter_reduce_(0, group[bad], bad, "amin")
+        group[bad] = first_bad[group[bad]]
+        pending[bad] = group[bad] != bad
+        proven[bad] = group[bad] == bad
+    return group, proven
+
+
+def isomorphic_duplicates(batches, labels=None, rounds: int = 0, attrs: bool = False, confirm: bool = True, keys=None, colors=None,
+                          budget_bytes: int = 256 << 20) -> IsoDuplicates:
+    """The classes of graphs that colour refinement cannot tell apart, whatever their numbering, of one batch or of a sequence of batches
+    (a sample and the training split; the epochs of a decoded corpus), on the device -> IsoDuplicates over their concatenation.  Keys
+    and node colours come from gtok_graph_wl (ops.graph_wl_keys: rounds, attrs; labels: one tensor per batch, or None) unless `keys`
+    (int64 [T, 2], or one [G, 2] per batch) and - with confirm - `colors` (int64 [total nodes], or one per batch) supply them; grouping
+    is ops.duplicate_graphs'.  confirm=True compares every member of a class with the class's first member: a member whose colours
+    differ under an equal key leaves the class; where both graphs have as many distinct colours as nodes (a DISCRETE colouring, found
+    with a sort over (graph, colour)) the colour ranks number both canonically and their entry lists in that numbering (with attrs the
+    directed entries with their bytes, and the node bytes) are compared - equal lists prove the isomorphism (proven = True), different
+    ones split the member off into a class of its own.  A member with a colouring that is not discrete (rings, most molecules: symmetric
+    atoms share a colour) stays in the class with proven = False: "WL-equivalent", which is not "isomorphic" (a 6-cycle and two
+    triangles are WL-equivalent).  confirm=False trusts the 128 bits and proves nothing beyond the class heads."""
+    single = isinstance(batches, GraphBatch)
+    bl = [batches] if single else list(batches)
+    if not bl:
+        raise ValueError("isomorphic_duplicates: no batch")
+    if labels is None:
+        ll = [None] * len(bl)
+    else:
+        ll = [labels] if single else list(labels)
+        if len(ll) != len(bl):
+            raise ValueError("isomorphic_duplicates: one label tensor (or None) per batch")
+    flags = _wl_flags(bl, rounds, attrs)
+    dev = bl[0].device
+    if any(b.device != dev for b in bl):
+        raise ValueError("isomorphic_duplicates: batches on different devices")
+    ll = [_labels_of(b, l, dev) for b, l in zip(bl, ll)]
+    ptr = [0]
+    for b in bl:
+        ptr.append(ptr[-1] + b.num_graphs)
+    T = ptr[-1]
+    N = sum(b.num_nodes_total for b in bl)
+    if keys is None:
+        got = [_graph_wl_launch(b, l, int(rounds), flags, confirm) for b, l in zip(bl, ll)]
+        keys = torch.cat([g[0] for g in got])
+        colors = torch.cat([g[1] for g in got]) if confirm else None
+    else:
+        keys = torch.cat([torch.as_tensor(k).reshape(-1, 2) for k in keys]) if isinstance(keys, (list, tuple)) else torch.as_tensor(keys)
+        keys = keys.to(dev, dtype=torch.int64)
+        if tuple(keys.shape) != (T, 2):
+            raise ValueError(f"isomorphic_duplicates: keys must be int64 [{T}, 2]")
+        if confirm:
+            if colors is None:
+                raise ValueError("isomorphic_duplicates: confirm=True with keys= needs the node colours too (colors=)")
+            colors = torch.cat([torch.as_tensor(c).reshape(-1) for c in colors]) if isinstance(colors, (list, tuple)) else torch.as_tensor(colors)
+            colors = colors.to(dev, dtype=torch.int64).reshape(-1)
+            if int(colors.numel()) != N:
+                raise ValueError(f"isomorphic_duplicates: colors must be int64 [{N}]")
+    split = torch.repeat_interleave(torch.arange(len(bl), device=dev), torch.tensor([b.num_graphs for b in bl], device=dev))
+    group = _group_by_keys(keys)
+    ar = torch.arange(T, device=dev)
+    proven = group == ar
+    if confirm and T:
+        group, proven = _confirm_wl(bl, ll, ptr, group, colors, attrs, budget_bytes)
+    return IsoDuplicates(group, split, group == ar, ptr, proven)
+
+
+def unique_novel(generated: GraphBatch, references, rounds: int = 0, attrs: bool = False, keys=None, colors=None) -> Dict[str, torch.Tensor]:
+    """Uniqueness and novelty of a batch of generated (decoded) graphs against one reference batch or a sequence of them (the training
+    split), whatever numbering each graph has - ops.isomorphic_duplicates over [generated] + references, confirmed; device tensors,
+    nothing read back:
+      unique      bool [G]  the graph is the first of its class inside `generated`
+      novel       bool [G]  its class occurs in no reference batch
+      num_unique, num_novel   int64 scalars: their counts (the two rates are these over G)
+    Classes are those of colour refinement: a generated graph that no round tells apart from a reference graph counts as known.
+    keys= / colors=: as ops.isomorphic_duplicates takes them, for the concatenation."""
+    refs = [references] if isinstance(references, GraphBatch) else list(references)
+    dup = isomorphic_duplicates([generated] + refs, None, rounds, attrs, True, keys, colors)
+    G = generated.num_graphs
+    P, cls = dup._presence()
+    unique = dup.is_first[:G]
+    novel = ~P[cls[:G], 1:].any(1)
+    return dict(unique=unique, novel=novel, num_unique=unique.sum(), num_novel=novel.sum())
 
 
 def remap_zinc(ids: torch.Tensor, ln: torch.Tensor, idx_offset: int, node_idx_offset: int,

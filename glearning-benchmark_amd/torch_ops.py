@@ -698,6 +698,24 @@ def _(node_ptr, edge_ptr, rowptr, col, nattr, eattr, max_nodes, max_edges, flags
     return col.new_empty((node_ptr.shape[0] - 1, 2), dtype=torch.int64)
 
 
+@torch.library.custom_op("gtok::graph_wl_keys", mutates_args=(), device_types="cuda")
+def graph_wl_keys(node_ptr: Tensor, edge_ptr: Tensor, rowptr: Tensor, col: Tensor, nattr: Optional[Tensor], eattr: Optional[Tensor],
+                  max_nodes: int, max_edges: int, flags: int, labels: Optional[Tensor], rounds: int, attrs: bool) -> Tuple[Tensor, Tensor]:
+    """gtok_graph_wl: (keys int64 [G, 2], node colours int64 [N]) - the numbering-independent 128-bit key of every graph of the batch and
+    the final colour of every node (include/gtok.h).  flags: GTOK_CSR_SIMPLE_SYMMETRIC where the caller has established it (needed beyond
+    512 nodes and with attrs).  rounds: 0 = N_g rounds; attrs: the attribute bytes enter the colours (needs nattr and eattr).  labels
+    int32 [G] or None.  Nothing is read back."""
+    b = GraphBatch(int(node_ptr.numel()) - 1, max_nodes, max_edges, node_ptr, edge_ptr, rowptr, col, None, nattr, eattr, int(flags))
+    keys, colors = _ops.graph_wl_keys(b, rounds, labels, bool(attrs), with_colors=True)
+    return keys, colors
+
+
+@graph_wl_keys.register_fake
+def _(node_ptr, edge_ptr, rowptr, col, nattr, eattr, max_nodes, max_edges, flags, labels, rounds, attrs):
+    G = node_ptr.shape[0] - 1
+    return col.new_empty((G, 2), dtype=torch.int64), col.new_empty((rowptr.shape[0] - G,), dtype=torch.int64)
+
+
 # ---- packed (ragged) rows: include/gtok.h, "packed rows" -----------------------------------------------------------------
 @torch.library.custom_op("gtok::row_offsets", mutates_args=(), device_types="cuda")
 def row_offsets(lens: Tensor, ld: int, align: int) -> Tensor:

@@ -976,6 +976,52 @@ int gtok_graph_tasks(const gtok_csr *g, const int32_t *query_nodes, const int64_
 #define GTOK_KEYS_ATTRS 2
 int gtok_graph_keys(const gtok_csr *g, const int32_t *labels, int32_t flags, uint64_t *keys, int32_t *info, void *stream);
 
+/* ---- a key per graph that does not depend on the numbering: Weisfeiler-Lehman colour refinement ---------------------------------
+ * gtok_graph_keys identifies a NUMBERED graph, and every graph the SENT decoders return is numbered in visit-index space: the same
+ * molecule tokenized in two epochs decodes to two numberings and two keys, and a generated sequence has no input numbering to go
+ * back to.  gtok_graph_wl gives every graph of a batched CSR a 128-bit key that is an INVARIANT: isomorphic graphs always share it,
+ * however they are numbered, listed or oriented.  It is no isomorphism class and no canonical form either - graphs that are not
+ * isomorphic share it when `rounds` rounds of colour refinement cannot tell them apart (regular graphs of equal degree: a 6-cycle
+ * and two triangles), or by a collision of 64-bit words.  Grouping, confirming and the uniqueness / novelty counts of a sampled batch
+ * are torch plumbing on top (ops.isomorphic_duplicates, ops.unique_novel).  The arithmetic is csrc/gtok_graph_wl_hash.hpp, frozen in
+ * DESIGN.md section 5c.
+ * The graph of a CSR slice is the simple undirected closure gtok_graph_tasks defines (distinct neighbours, a loop flag per node).
+ * Every node starts with a colour made of its degree and loop flag; a round gives it the mix of its colour and the keyed sum of its
+ * neighbours' colours; the key digests the multiset of final colours, N, the rounds run and the label.  rounds in [0,
+ * GTOK_WL_MAX_ROUNDS]: 0 = N_g rounds for every graph (the colouring is stable by then; <= 512 nodes only).  A path of N nodes needs
+ * about N / 2 rounds to tell its nodes apart; 3 separates what molecules and the graph-token corpora hold.
+ * flags = 0 or GTOK_WL_ATTRS: the node attribute bytes enter the first colours and the byte of the entry (v, u), as row v lists it,
+ * enters what u adds to v (needs g->nattr, g->eattr and a GTOK_CSR_SIMPLE_SYMMETRIC batch; the flag is trusted: each direction's own
+ * byte is read).
+ * labels int32 [G] or NULL (label 0).  keys uint64 [G, 2].  node_colors uint64 [node_ptr[G]] or NULL: the final colour of node v of
+ * graph g at node_ptr[g] + v - equal colours in two graphs of equal key pair up nodes no round could tell apart; a graph with N
+ * distinct colours is numbered canonically by their ranks.  info int32 [4], zeroed by the CALLER, as gtok_graph_keys': [0] bit value
+ * 2 = damaged arrays (a bad slice: the graph counts as empty and gets no colours; a bad row is skipped; a bad column is skipped),
+ * [1] the graphs with such damage.  Nothing is read through an unchecked index; nothing is written outside keys[2 g .. 2 g + 1], the
+ * graph's own node_colors slice, info and the workspace.
+ * One wave per graph (independent waves), the kernel chosen for the whole batch:
+ *   reg   max_nodes <= 64, structure only, any listing: closure rows in a 64-bit register per lane, a 64-entry term table in LDS
+ *   lds   <= 512, structure only, any listing: the bit matrix in LDS plus a term table of 8 bytes per node (36 KB per wave at most)
+ *   csr   GTOK_CSR_SIMPLE_SYMMETRIC batches of any size up to GTOK_SENT_LARGE_MAX_NODES, and every GTOK_WL_ATTRS call: a pull over
+ *         the CSR rows, lane l owning nodes l + 64 j, two 8-byte tables per node - in LDS up to 4,096 nodes (64 KB, one wave per
+ *         workgroup there), beyond that in `workspace`: 16 bytes per node of max_nodes for each of min(G, GTOK_WL_LARGE_WAVES) waves,
+ *         wave w taking graphs w, w + waves, ...
+ * A hub's row is one lane's loop on all three.  GTOK_WL_KERNEL=reg|lds|csr forces one (tests); one that cannot hold the batch is
+ * GTOK_E_UNSUPPORTED.  gtok_graph_wl_workspace: pure host arithmetic, the bytes `workspace` must have (16-byte aligned; 0, and
+ * workspace may be NULL, up to 4,096 nodes); GTOK_E_INVAL for a negative argument, GTOK_E_TOO_LARGE beyond GTOK_SENT_LARGE_MAX_NODES.
+ * Errors, all before any device is asked for: GTOK_E_INVAL for null pointers / negative sizes / a reordered batch / unknown flag bits /
+ * rounds outside [0, GTOK_WL_MAX_ROUNDS] / GTOK_WL_ATTRS without both attribute arrays / a short or misaligned workspace;
+ * GTOK_E_TOO_LARGE for max_nodes beyond GTOK_SENT_LARGE_MAX_NODES; GTOK_E_UNSUPPORTED for an unflagged batch beyond 512 nodes,
+ * GTOK_WL_ATTRS on an unflagged batch, rounds == 0 beyond 512 nodes, a forced kernel that cannot hold the batch; num_graphs == 0 is a
+ * no-op.  The call only enqueues one launch on `stream` (whose device is used): no allocation, no host read-back, no library-owned
+ * counters - it can be captured into a hipGraph.  (Added without an ABI version step: no struct changes.)                        */
+#define GTOK_WL_ATTRS 2            /* flags: node and edge attribute bytes enter the colours */
+#define GTOK_WL_MAX_ROUNDS 512
+#define GTOK_WL_LARGE_WAVES 1024
+int64_t gtok_graph_wl_workspace(int32_t max_nodes, int32_t num_graphs);
+int gtok_graph_wl(const gtok_csr *g, const int32_t *labels, int32_t rounds, int32_t flags, uint64_t *keys, uint64_t *node_colors,
+                  int32_t *info, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* Which SENT kernel gtok_sent() will run for this batch ("sent_lane_kernel": lane per graph over the CSR, needs
  * GTOK_CSR_SIMPLE_SYMMETRIC, <= 64 nodes and a large batch; "sent_blane_kernel<W=..>": lane per graph over the
  * adjacency bit-matrix mirror, unlabelled, <= 256 nodes; "sent_reg_kernel": wave per graph, <= 64 nodes;
